@@ -11,12 +11,27 @@ One process per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment), data 
 RCCL: every rank holds `--batch` images (weak scaling), gradients of the flat arena are summed in
 buckets of at most 48 MB cut at backward-unit boundaries in reverse execution order, each all-reduced
 on a side stream while the backward goes on (engine.dp_unit_buckets).  Inputs are synthetic and resident in HBM before the
-timed region.  Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times exactly `--steps` steps, writes the last step's outputs if
+`--dump-outputs DIR` is given, and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...).  With `--full` the line also carries what takes runs or checks of its own:
+  sustained    - a second, longer timed region of the same step (clocks and thermals)
+  host_input   - the same step fed from pinned host memory (PCIe-inclusive rates), N=1 only
   roofline     - the dominant kernel of the step, timed live with HIP events behind every launch
                  (vu_prof_enable) over extra instrumented steps; achieved = algorithmic flops (or
                  bytes) / launch time, against the MI355X dense bf16 MFMA peak (or HBM peak)
+  parity       - the GPU eval forward against the CPU oracle, N=1 only
   cpu_baseline - the CPU oracle (torch CPU fp32 restatement of the reference) timed on this
                  host's cores on a bounded sample (B=8, a few iterations), N=1 only
+Without `--full` these fields are null.
+
+`--dump-outputs DIR` (rank 0): what the timed step left behind after its last timed step, as float32
+.npy files - loss, output (the model's prediction), params and grads (the flat parameter / gradient
+arenas after AdamW), bn_stats (BatchNorm running statistics).  An array of more than DUMP_CAP elements
+is written as a fixed, seeded sample of DUMP_CAP elements (the same indices on every run).  Inputs,
+weights and dropout masks are seeded, so two runs with the same arguments are comparable output for
+output.
 """
 import argparse
 import json
@@ -32,6 +47,7 @@ import torch  # noqa: E402
 TRAIN_GFLOP_PER_IMG = {"lite": 27.93, "base": 23.27, "large": 42.43, "seg512": 107.71}
 MFMA_PEAK_TFLOPS = 2500.0      # dense bf16, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0
+DUMP_CAP = 3 << 20             # elements per dumped array (12 MB in float32; five arrays stay under 64 MB)
 
 
 def parse():
@@ -60,8 +76,43 @@ def parse():
     ap.add_argument("--no-sustained", action="store_true", help="skip the second, longer timed region (profiler runs)")
     ap.add_argument("--sustained-s", type=float, default=8.0, help="length of the second timed region in seconds")
     ap.add_argument("--profile-steps", type=int, default=2)
-    ap.add_argument("--dump-profile", default=None, help="write the full per-kernel table (JSON) here")
-    return ap.parse_args()
+    ap.add_argument("--dump-profile", default=None, help="--full: write the full per-kernel table (JSON) here")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: sustained region, host-input legs, roofline, "
+                         "parity against the CPU oracle, CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, large arrays sampled)")
+    a = ap.parse_args()
+    if a.dump_profile and not a.full:
+        ap.error("--dump-profile needs --full (the per-kernel table comes from the roofline steps)")
+    return a
+
+
+def dump_sample(t: torch.Tensor, cap: int = DUMP_CAP, seed: int = 0) -> torch.Tensor:
+    """`t` flattened, or a fixed, seeded, sorted sample of `cap` of its elements: one index drawn in each of `cap` equal
+    strides of the flat array, so that the sample covers the whole tensor and is the same on every run."""
+    t = t.detach().reshape(-1)
+    n = t.numel()
+    if n <= cap:
+        return t
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    lo = torch.arange(cap, dtype=torch.int64) * n // cap
+    hi = (torch.arange(1, cap + 1, dtype=torch.int64) * n) // cap
+    idx = lo + (torch.rand(cap, generator=g, dtype=torch.float64) * (hi - lo)).to(torch.int64)
+    return t[idx.to(t.device)]
+
+
+def dump_outputs(out_dir: str, ts, model) -> dict:
+    """The arrays a caller of the timed step receives after its last step, as float32 .npy files (see the module docstring)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": ts.loss, "output": ts._gout, "params": model._arena, "grads": model._garena, "bn_stats": model._bn}
+    shapes = {}
+    for i, (name, t) in enumerate(arrays.items()):
+        v = dump_sample(t, seed=i).float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        shapes[name] = {"shape": list(t.shape), "written": int(v.size)}
+    return shapes
 
 
 def host_cores() -> int:
@@ -265,6 +316,9 @@ def main():
         t = torch.tensor([dt_s], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt_s = t.item()
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, ts, model)      # before anything below runs another step
     loss = float(ts.loss.item())
     images = a.batch * world * a.steps
     value = images / dt_s
@@ -272,7 +326,7 @@ def main():
     # timed region was under 2 s, a second, longer region of the same step is timed and reported beside it (`sustained`;
     # `value` / `steps` stay the contract's K steps)
     sustained = None
-    if dt_s < a.sustained_s and not a.no_sustained:
+    if a.full and dt_s < a.sustained_s and not a.no_sustained:
         # (round 6: >= 8 s by default, so that a 5 s GPU-busy sampler beside the run sees the card working - the contract's
         # 20 steps are 0.2 s of a run whose wall clock is mostly the CPU baseline)
         n2 = int(min(4000, max(a.steps, a.sustained_s * 1.1 / (dt_s / a.steps))))
@@ -292,7 +346,7 @@ def main():
     # CHW batch ImageFitter.unpack moves (dataset.py:78-91), (b) as decoded uint8 HWC images that the
     # device-side input pipeline (vu_denoise_prepare, train transform) turns into the batch
     host_in = None
-    if rank == 0 and not dp and not a.no_host_input and not seg:
+    if a.full and rank == 0 and not dp and not a.no_host_input and not seg:
         from vit_unet.torch.dataset import DenoisingBatchTransform
         n_h = max(3, min(a.steps, 10))
         hx, hy = x.cpu().pin_memory(), y.cpu().pin_memory()
@@ -324,7 +378,7 @@ def main():
 
     roof = None
     rep = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # extra instrumented steps: every rank runs them (they contain the gradient all-reduce), rank 0 with one HIP
         # event behind every launch on its compute stream
         L = _lib.lib()
@@ -395,7 +449,7 @@ def main():
                                   "GBs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["bytes"] else None}
                                  for k, v in top[:8]]})
     cpu, parity = None, None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         parity = eval_parity(a.model, dt, B=1 if seg else 2, operands=operands)
         if not seg:
             cpu = cpu_baseline(a.model, host_cores())
@@ -414,7 +468,7 @@ def main():
                           "per_gpu_batch": a.batch, "global_batch": a.batch * world, "parallelism": f"dp{world}", "rccl_path": dp, "comm": comm, "grad_wire": a.grad_wire,
                           "hip_graph": use_graph, "tail_overlap": bool(not use_graph and ts.prefers_eager(a.batch)), "attn_operands": operands, "final_loss": loss},
                "roofline": roof, "cpu_baseline": cpu, "parity": parity, "host_input": host_in, "sustained": sustained,
-               "workspace": model.workspace_report(a.batch)}
+               "workspace": model.workspace_report(a.batch), "full": a.full, "dumped_outputs": dumped}
         print(json.dumps(out), flush=True)
     if dp:
         # Leave without tearing the RCCL process group down: destroy_process_group() aborted intermittently in the GPU test

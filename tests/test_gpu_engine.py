@@ -125,3 +125,33 @@ def test_constructor_rejects_what_the_hip_path_cannot_run():
         M.HViT_UNet(**dict(KW, num_heads=3, patch_size=12, im_size=36))     # 3 heads: not in {1,2,4,8}
     with pytest.raises(AssertionError):
         M.HViT_UNet(**dict(KW, patch_size=8, depth=2))                       # model.py:281-283 asserts stay asserts
+
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's loss / output / parameters / gradients / BatchNorm statistics as
+    float32 .npy files under 64 MB, the result line counts exactly `--steps` timed steps, and two runs with the same arguments
+    write the same arrays (seeded inputs, weights and dropout).  The default workload (Base, 64 images): the one whose outputs
+    are compared between builds."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["full"] is False
+        assert out["roofline"] is None and out["cpu_baseline"] is None and out["sustained"] is None
+        runs.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = runs
+    assert set(a) == {"loss", "output", "params", "grads", "bn_stats"}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), (k, np.abs(a[k] - b[k]).max())
+    assert a["output"].size == 3 << 20 and a["params"].size == 3 << 20 and a["loss"].size == 1     # sampled: 64x3x224x224, 39.6 M

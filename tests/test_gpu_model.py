@@ -32,7 +32,10 @@ def serr(got, ref):
 def load_case(golden_dir, name):
     with open(os.path.join(golden_dir, "manifest.json")) as f:
         man = json.load(f)
-    return man, dict(np.load(os.path.join(golden_dir, name + ".npz")))
+    g = {}
+    for f in [name + ".npz"] + sorted(f for f in os.listdir(golden_dir) if f.startswith(name + "_part") and f.endswith(".npz")):
+        g.update(np.load(os.path.join(golden_dir, f)))     # a fixture over 1 MB is stored in parts (make_golden.py)
+    return man, g
 
 
 def build(kw, weights, dtype=torch.float32, **over):

@@ -446,7 +446,9 @@ def test_bf16_vs_fp32_loss_trajectory_base():
 # (e) surface that round 1 left untested: FeedForward alone, preprocessing='none', the ViT_UNet(...) alias
 # ------------------------------------------------------------------------------------------------
 def test_feedforward_module_vs_golden(golden_dir):
-    g = dict(np.load(os.path.join(golden_dir, "ops.npz")))
+    g = {}
+    for f in ("ops.npz", "ops_part2.npz"):                 # the per-op fixture is stored in two parts (make_golden.py)
+        g.update(np.load(os.path.join(golden_dir, f)))
     for tag, (N, C_, s, h, hid) in {"n49": (49, 3, 8, 4, 16), "d12": (16, 3, 4, 4, 8)}.items():
         D = C_ * s * s
         ff = M.FeedForward(D, hid, 0.0)

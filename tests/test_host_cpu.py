@@ -252,3 +252,17 @@ def test_library_links_no_vendor_blas():
     needed = [l.split("[")[1].split("]")[0] for l in out.splitlines() if "(NEEDED)" in l]
     assert needed, out
     assert not [n for n in needed if any(t in n.lower() for t in ("blas", "miopen", "tensile", "rccl"))], needed
+
+
+def test_bench_dump_sample_is_fixed_and_spans_the_array():
+    """bench.py --dump-outputs writes arrays above its cap as a seeded sample: the same indices every time, one per stride,
+    inside the array; smaller arrays whole."""
+    import bench
+    t = torch.arange(10_000, dtype=torch.float64)
+    s1, s2 = bench.dump_sample(t, cap=1000, seed=3), bench.dump_sample(t, cap=1000, seed=3)
+    assert torch.equal(s1, s2) and s1.numel() == 1000
+    idx = s1.long()
+    assert (idx[1:] > idx[:-1]).all() and idx[0] >= 0 and idx[-1] < t.numel()
+    assert torch.equal(idx // 10, torch.arange(1000))
+    assert not torch.equal(bench.dump_sample(t, cap=1000, seed=4), s1)
+    assert torch.equal(bench.dump_sample(t.view(100, 100), cap=20_000), t)

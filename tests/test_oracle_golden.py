@@ -22,7 +22,10 @@ def close(got, ref, tol=TOL):
 def _load(golden_dir, name):
     with open(os.path.join(golden_dir, "manifest.json")) as f:
         man = json.load(f)
-    return man, dict(np.load(os.path.join(golden_dir, name + ".npz")))
+    g = {}
+    for f in [name + ".npz"] + sorted(f for f in os.listdir(golden_dir) if f.startswith(name + "_part") and f.endswith(".npz")):
+        g.update(np.load(os.path.join(golden_dir, f)))     # a fixture over 1 MB is stored in parts (make_golden.py)
+    return man, g
 
 
 @pytest.mark.parametrize("name", TINY)
