@@ -267,6 +267,29 @@ int vu_seg_prepare(const int16_t* image, const uint8_t* mask, float* x, float* y
                    size_t scratch_bytes, const double* inv_affine, int B, int Hs, int Ws, int oh,
                    int ow, float lo, float hi, float ls, void* stream);
 
+/* Whole-image restoration (csrc/vu_tile.hip; no reference counterpart: the reference only ever resizes to im_size): sliding-window
+ * inference.  An H x W image is covered by T x T windows (T = im_size) overlapping by `overlap` pixels, 0 <= overlap <= T / 2, stride
+ * S = T - overlap.  Per axis of length L: L <= T gives one window at 0 whose T - L missing rows / columns are reflected without
+ * repeating the edge (m = 2 (L - 1), k = i mod m, source k if k < L else m - k; L == 1 replicates) and of whose output only the first
+ * L rows / columns are used; L > T gives n = ceil((L - T) / S) + 1 windows at min(i S, L - T) - the last one shifted inwards, not
+ * padded.  The 2-D plan is the outer product, row-major (window t = ty * nx + tx); a pixel lies in at most 3 windows per axis.
+ *   plan_count   ny, nx of the plan (host pointers)            plan_axis   origins[0 .. n) of one axis (host), returns n
+ * Both are host code (no GPU call).
+ *   gather_u8    img (H,W,C) uint8 HWC as decoded -> windows [t0, t0 + n) of the plan as tiles (n,C,T,T) float32 under the
+ *                validation transform of the input pipeline (what the denoise-prepare call above gives `noisy` without a warp)
+ *   gather_f32   img (C,H,W) float32 -> the same windows, values copied unchanged
+ *   blend        tiles (ny nx,C,T,T) float32, the outputs for the WHOLE plan -> out_f32 (C,H,W) and / or out_u8 (H,W,C) (either may
+ *                be NULL): per pixel acc += w v, ws += w over the covering windows in ascending plan order, out = acc / ws, all
+ *                float32, w = wy wx with w(i) = min(i + 1, T - i, overlap + 1) / (overlap + 1); out_u8 = clamp(floor(255 out + 0.5),
+ *                0, 255).  A gather (no atomics): bit-identical on every run.  The outputs must not alias `tiles`.
+ * 1 <= C <= 4.  T % 4 == 0 and 16-byte aligned buffers take 16-byte accesses; anything else is handled by scalar ones. */
+int vu_tile_plan_count(int H, int W, int T, int overlap, int* ny, int* nx);
+int vu_tile_plan_axis(int L, int T, int overlap, int* origins, int capacity);
+int vu_tile_gather_u8(const uint8_t* img, float* tiles, int H, int W, int C, int T, int overlap, int t0, int n, float mean,
+                      float std, void* stream);
+int vu_tile_gather_f32(const float* img, float* tiles, int H, int W, int C, int T, int overlap, int t0, int n, void* stream);
+int vu_tile_blend(const float* tiles, float* out_f32, uint8_t* out_u8, int H, int W, int C, int T, int overlap, void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

@@ -1,0 +1,13 @@
+// The Normalize + /255 step of the denoising input pipeline, shared by csrc/vu_data.hip (vu_denoise_prepare) and
+// csrc/vu_tile.hip (vu_tile_gather_u8): one definition, so that a window cut from a large image carries bit for bit the
+// values the validation transform gives the same pixels.
+#pragma once
+#include "vu_common.h"
+
+// albumentations Normalize(mean, std, max_pixel_value = 255) in float32: (v - mean*255) * (1/(std*255)), then the
+// dataset's /255 (dataset.py:66)
+static inline float vu_normalize_m255(float mean) { return mean * 255.0f; }
+static inline float vu_normalize_rden(float std) { return 1.0f / (std * 255.0f); }
+__device__ __forceinline__ float vu_normalize_u8(int v, float m255, float rden) {
+  return __fdiv_rn(__fmul_rn(__fsub_rn((float)v, m255), rden), 255.f);
+}

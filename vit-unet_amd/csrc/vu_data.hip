@@ -10,6 +10,7 @@
 // warp: 10-bit coordinates, 1/32 sub-pixel), restated - OpenCV itself is not in the reference tree
 // nor in this image, so parity with it is unpinned; parity with oracle/ is bit-exact.
 #include "vu_common.h"
+#include "vu_data.h"
 #include "../../include/vit_unet_amd.h"
 
 namespace {
@@ -105,8 +106,7 @@ __global__ __launch_bounds__(256) void warp_norm_kernel(const uint8_t* __restric
   const size_t plane = (size_t)im * im;
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
-    // Normalize: (v - mean*255) * (1/(std*255)) in float32, then /255 (dataset.py:66)
-    if (n) x[((size_t)b * CH + k) * plane + p] = __fdiv_rn(__fmul_rn(__fsub_rn((float)vn[k], m255), rden), 255.f);
+    if (n) x[((size_t)b * CH + k) * plane + p] = vu_normalize_u8(vn[k], m255, rden);
     // the clean image is divided as uint8/255. (float64) and cast to float32 by unpack (dataset.py:66,80)
     if (c) y[((size_t)b * CH + k) * plane + p] = (float)__ddiv_rn((double)vc[k], 255.0);
   }
@@ -248,7 +248,7 @@ int vu_denoise_prepare(const uint8_t* noisy, const uint8_t* clean, float* x, flo
       if (which) rc = d; else rn = d;
     }
   }
-  const float m255 = mean * 255.0f, rden = 1.0f / (std * 255.0f);
+  const float m255 = vu_normalize_m255(mean), rden = vu_normalize_rden(std);
   if (channels == 3) hipLaunchKernelGGL(warp_norm_kernel<3>, grid, dim3(256), 0, st, rn, rc, x, y, inv_affine, im, m255, rden);
   else hipLaunchKernelGGL(warp_norm_kernel<1>, grid, dim3(256), 0, st, rn, rc, x, y, inv_affine, im, m255, rden);
   if (vu_prof_on()) vu_prof_note("warp_norm_kernel", 0.0, (double)one * ((noisy ? 5.0 : 0.0) + (clean ? 5.0 : 0.0)));

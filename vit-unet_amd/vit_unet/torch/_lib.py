@@ -114,6 +114,11 @@ SIGNATURES = {
     "vu_denoise_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "vu_seg_prepare_scratch_bytes": (_sz, [_i, _i, _i]),
     "vu_seg_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
+    "vu_tile_plan_count": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vu_tile_plan_axis": (_i, [_i, _i, _i, C.POINTER(C.c_int), _i]),
+    "vu_tile_gather_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "vu_tile_gather_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vu_tile_blend": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "vu_add": (_i, [_i, _vp, _vp, _vp, _ll, _vp]),
     "vu_dropout": (_i, [_i, _vp, _vp, _ll, _f, _u64, _u64, _vp]),
     "vu_gelu_fwd": (_i, [_i, _vp, _vp, _ll, _vp]),

@@ -64,6 +64,32 @@ def ssim(model, dataloader, device="cuda"):
     return np.concatenate(score) if score else np.zeros(0)
 
 
+def _tiled_scores(model, pairs, overlap, batch, score):
+    """Full-resolution metric over (noisy_u8, clean_u8) pairs of (H,W,C) images: the restorer's float image against clean / 255
+    (what `DenoisingBatchTransform` gives the model as target), one (1,C,H,W) call of `score` per pair."""
+    from .restore import TiledRestorer
+    r = TiledRestorer(model, overlap=overlap, batch=batch)
+    res = []
+    for noisy, clean in pairs:
+        out = r(noisy, output="f32")
+        c = torch.from_numpy(np.ascontiguousarray(clean)) if isinstance(clean, np.ndarray) else clean
+        assert c.dtype == torch.uint8 and c.dim() == 3, "expected (H,W,C) uint8 clean images"
+        y = (c.to(out.device).permute(2, 0, 1).double() / 255.0).float().contiguous()
+        res.append(score(y[None], out[None]).cpu().numpy())
+    return np.concatenate(res) if res else np.zeros(0)
+
+
+def psnr_tiled(model, pairs, overlap: int = 32, batch: int = 64):
+    """`psnr` at full resolution: every pair of (H,W,C) uint8 images goes through sliding-window inference
+    (restore.TiledRestorer) instead of a resize to im_size.  Returns one value per pair."""
+    return _tiled_scores(model, pairs, overlap, batch, psnr_batch)
+
+
+def ssim_tiled(model, pairs, overlap: int = 32, batch: int = 64):
+    """`ssim` at full resolution (see `psnr_tiled`)."""
+    return _tiled_scores(model, pairs, overlap, batch, ssim_batch)
+
+
 class _Dice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target, apply_sigmoid):

@@ -642,10 +642,16 @@ class HViT_UNet(nn.Module):
         self._shadow_version = ver
 
     # ---- execution -------------------------------------------------------------------------
-    def _run_forward(self, x: torch.Tensor, training: bool, seed: int, salt: Optional[torch.Tensor] = None):
+    def _run_forward(self, x: torch.Tensor, training: bool, seed: int, salt: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None):
+        """`out`: a float32 buffer of x's shape to write into (restore.py: a slice of the window-output buffer)."""
         B = x.shape[0]
         xc = x.detach().float().contiguous()
-        y = torch.empty_like(xc)
+        if out is None:
+            y = torch.empty_like(xc)
+        else:
+            assert out.shape == xc.shape and out.dtype == torch.float32 and out.device == xc.device, "out must match x"
+            y = out
         ws = self._workspace(B, training)
         self.refresh_shadow()
         self._gen += 1
@@ -685,6 +691,16 @@ class HViT_UNet(nn.Module):
             self._link_grads()
             return _ModelFn.apply(X, self._anchor, self, training, seed)
         return self._run_forward(X, training, seed)
+
+    def restore(self, image, overlap: int = 32, batch: int = 64):
+        """Restore a whole image of any size by sliding-window inference (restore.TiledRestorer, built once per
+        (overlap, batch) and kept).  `forward` is unchanged: it still resizes inputs of another size."""
+        from .restore import TiledRestorer
+        key = (int(overlap), int(batch))
+        cache = self.__dict__.setdefault("_restorers", {})
+        if key not in cache:
+            cache[key] = TiledRestorer(self, overlap=overlap, batch=batch)
+        return cache[key](image)
 
 
 def ViT_UNet(depth, depth_te, size_bottleneck, preprocessing, num_patches, patch_size, num_channels=3,
