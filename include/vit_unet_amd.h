@@ -290,6 +290,26 @@ int vu_tile_gather_u8(const uint8_t* img, float* tiles, int H, int W, int C, int
 int vu_tile_gather_f32(const float* img, float* tiles, int H, int W, int C, int T, int overlap, int t0, int n, void* stream);
 int vu_tile_blend(const float* tiles, float* out_f32, uint8_t* out_u8, int H, int W, int C, int T, int overlap, void* stream);
 
+/* Native-resolution training patches and the self-ensemble (csrc/vu_patch.hip; no reference counterpart).  Both rest on the dihedral
+ * transforms of a T x T window: op in 0 .. 7, k = op & 3 counter-clockwise quarter turns applied after a left-right flip when op & 4,
+ *   D_op(p) = np.rot90(np.fliplr(p) if op & 4 else p, k = op & 3),   m = flipped or plain p with m[a,b] = p[a, T-1-b]:
+ *   k = 0: out[i,j] = m[i,j]   k = 1: m[j, T-1-i]   k = 2: m[T-1-i, T-1-j]   k = 3: m[T-1-j, i].
+ *   dihedral_inverse   the op that undoes `op`: op itself when op & 4, else (4 - op) & 3; negative outside 0 .. 7.  Host code, no GPU call.
+ *   patch_pairs_u8     ONE image pair, noisy / clean (H,W,C) uint8 HWC as decoded; crops: (n,3) int32 (y0, x0, op) in DEVICE memory.
+ *                      x[i] = D_op(noisy[y0:y0+T, x0:x0+T]) under the validation transform of the input pipeline (Normalize, /255),
+ *                      y[i] = the same cut and op of clean, /255 only; both (n,C,T,T) float32: what the denoise-prepare call above
+ *                      gives each side without a warp, bit for bit.  A pair may be omitted (noisy == x == NULL or clean == y == NULL).
+ *                      1 <= C <= 4, H >= T and W >= T (an image smaller than a patch is refused, not reflected), std > 0, n >= 1.
+ *                      The host cannot read the table, so the KERNEL CLAMPS it: y0 to [0, H-T], x0 to [0, W-T], op to op & 7 - no
+ *                      table content makes it read outside the image (callers that want an error check the table before uploading).
+ *   dihedral_f32       src, dst (n,C,T,T) float32, one op for the call: v = D_op(src plane), r = accumulate ? dst + v : v,
+ *                      dst = scale == 1 ? r : r * scale, every operation rounded once in float32.  dst must not overlap src.
+ * No atomics: bit-identical on every run.  Any T; T % 4 == 0 and 16-byte aligned buffers take 16-byte accesses, anything else scalar. */
+int vu_dihedral_inverse(int op);
+int vu_patch_pairs_u8(const uint8_t* noisy, const uint8_t* clean, float* x, float* y, int H, int W, int C, int T, const int* crops,
+                      int n, float mean, float std, void* stream);
+int vu_dihedral_f32(const float* src, float* dst, int n, int C, int T, int op, int accumulate, float scale, void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

@@ -1,6 +1,6 @@
-// The Normalize + /255 step of the denoising input pipeline, shared by csrc/vu_data.hip (vu_denoise_prepare) and
-// csrc/vu_tile.hip (vu_tile_gather_u8): one definition, so that a window cut from a large image carries bit for bit the
-// values the validation transform gives the same pixels.
+// The Normalize + /255 step of the denoising input pipeline, shared by csrc/vu_data.hip (vu_denoise_prepare),
+// csrc/vu_tile.hip (vu_tile_gather_u8) and csrc/vu_patch.hip (vu_patch_pairs_u8): one definition, so that a window or a
+// training patch cut from a large image carries bit for bit the values the validation transform gives the same pixels.
 #pragma once
 #include "vu_common.h"
 
@@ -11,3 +11,5 @@ static inline float vu_normalize_rden(float std) { return 1.0f / (std * 255.0f);
 __device__ __forceinline__ float vu_normalize_u8(int v, float m255, float rden) {
   return __fdiv_rn(__fmul_rn(__fsub_rn((float)v, m255), rden), 255.f);
 }
+// the clean image is divided as uint8/255. (float64) and cast to float32 by unpack (dataset.py:66,80)
+__device__ __forceinline__ float vu_unit_u8(int v) { return (float)__ddiv_rn((double)v, 255.0); }

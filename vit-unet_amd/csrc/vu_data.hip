@@ -107,8 +107,7 @@ __global__ __launch_bounds__(256) void warp_norm_kernel(const uint8_t* __restric
 #pragma unroll
   for (int k = 0; k < CH; ++k) {
     if (n) x[((size_t)b * CH + k) * plane + p] = vu_normalize_u8(vn[k], m255, rden);
-    // the clean image is divided as uint8/255. (float64) and cast to float32 by unpack (dataset.py:66,80)
-    if (c) y[((size_t)b * CH + k) * plane + p] = (float)__ddiv_rn((double)vc[k], 255.0);
+    if (c) y[((size_t)b * CH + k) * plane + p] = vu_unit_u8(vc[k]);
   }
 }
 

@@ -6,18 +6,21 @@ The reference decodes, resizes, augments and normalises every image on the host
 bottleneck.  Here the host only decodes (PNG -> uint8 HWC, out of scope) and draws the augmentation
 parameters; `DenoisingBatchTransform` runs resize -> ShiftScaleRotate -> Normalize -> /255 -> CHW
 for the whole batch with the HIP kernels of csrc/vu_data.hip (C ABI `vu_denoise_prepare`) and
-returns the `{'x','y'}` dict `ImageFitter.unpack` expects.  No CPU fallback.
+returns the `{'x','y'}` dict `ImageFitter.unpack` expects.  `DenoisingPatchTransform` is the
+native-resolution recipe instead of the resize: random aligned crops of the pair, each under one
+of the eight flips / rotations of the square (csrc/vu_patch.hip, C ABI `vu_patch_pairs_u8`).
+No CPU fallback.
 """
 from __future__ import annotations
 
 import math
 import random
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import VuError, check, lib, ptr, stream_ptr
 from .fitter import ImageFitter  # noqa: F401  (the reference keeps ImageFitter in this module)
 
 
@@ -90,6 +93,96 @@ class DenoisingBatchTransform:
         return {"x": x, "y": y}
 
 
+def dihedral_inverse(op: int) -> int:
+    """The op (0..7) that undoes dihedral op `op` (include/vit_unet_amd.h: vu_dihedral_inverse; host code, no GPU)."""
+    inv = lib().vu_dihedral_inverse(int(op))
+    if inv < 0:
+        raise VuError(f"a dihedral op is in 0 .. 7 (got {op})")
+    return inv
+
+
+class DenoisingPatchTransform:
+    """Native-resolution training patches: `per_image` aligned crops of `patch` x `patch` pixels out of every noisy / clean
+    pair, each under one of the eight dihedral ops (op & 3 counter-clockwise quarter turns after a left-right flip when
+    op & 4), normalised like the validation transform of `DenoisingBatchTransform` (Normalize on noisy, /255 on both) - no
+    resize anywhere.  Call with `(noisy, clean)`: (B,H,W,C) uint8 batches or lists of (H,W,C) uint8 images whose sizes may
+    differ from pair to pair (numpy or torch, host or device); returns {'x','y'} (B*per_image,C,patch,patch) float32 on the
+    device, the patches of image 0 first.
+
+    `train=True` draws (y0, x0, op) per patch from the transform's own `random.Random(seed)`; `train=False` is ONE centred
+    crop per image (y0 = (H-T)//2, x0 = (W-T)//2) with op 0.  `crops=` (B,per_image,3) replaces the draw.  Out-of-range
+    table entries, mismatched pairs and images smaller than a patch are refused here, before any launch (the kernel itself
+    clamps what it is given).  One `vu_patch_pairs_u8` call per pair, into slices of one output tensor."""
+
+    def __init__(self, patch: int = 224, per_image: int = 8, train: bool = True, mean: float = 0.456, std: float = 0.224,
+                 device="cuda", seed: Optional[int] = None):
+        self.patch, self.train = int(patch), bool(train)
+        self.per_image = int(per_image) if self.train else 1
+        if self.patch < 1 or self.per_image < 1:
+            raise VuError(f"patch and per_image must be at least 1 (got {patch}, {per_image})")
+        if not float(std) > 0:
+            raise VuError(f"std must be positive (got {std})")
+        self.mean, self.std, self.device = float(mean), float(std), device
+        self.rng = random.Random(seed)
+
+    def draw(self, sizes) -> np.ndarray:
+        """The (B,per_image,3) int32 crop table for images of `sizes` = [(H,W), ...] (host code, no GPU)."""
+        T = self.patch
+        out = np.zeros((len(sizes), self.per_image, 3), dtype=np.int32)
+        for b, (H, W) in enumerate(sizes):
+            if H < T or W < T:
+                raise VuError(f"image {b} ({H} x {W}) is smaller than a patch of {T}")
+            for p in range(self.per_image):
+                if self.train:
+                    out[b, p] = (self.rng.randint(0, H - T), self.rng.randint(0, W - T), self.rng.randint(0, 7))
+                else:
+                    out[b, p] = ((H - T) // 2, (W - T) // 2, 0)
+        return out
+
+    def _images(self, a) -> List[torch.Tensor]:
+        if isinstance(a, np.ndarray) or torch.is_tensor(a):
+            assert a.ndim == 4, "expected a (B,H,W,C) uint8 batch or a list of (H,W,C) uint8 images"
+        out = []
+        for im in a:
+            t = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im
+            assert torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() == 3, "expected (H,W,C) uint8 images"
+            out.append(t.to(self.device, non_blocking=True).contiguous())
+        return out
+
+    def __call__(self, noisy, clean, crops=None) -> Dict[str, torch.Tensor]:
+        ns, cs = self._images(noisy), self._images(clean)
+        assert len(ns) == len(cs) and len(ns) > 0, f"{len(ns)} noisy and {len(cs)} clean images"
+        T, P = self.patch, self.per_image
+        for b, (n, c) in enumerate(zip(ns, cs)):
+            assert n.shape == c.shape, f"pair {b}: noisy {tuple(n.shape)} and clean {tuple(c.shape)} differ"
+            assert n.shape[2] == ns[0].shape[2], f"pair {b}: {n.shape[2]} channels, pair 0 has {ns[0].shape[2]}"
+            if n.shape[0] < T or n.shape[1] < T:
+                raise VuError(f"image {b} ({n.shape[0]} x {n.shape[1]}) is smaller than a patch of {T}")
+        B, Cn = len(ns), int(ns[0].shape[2])
+        if not 1 <= Cn <= 4:
+            raise VuError(f"1 to 4 channels (got {Cn})")
+        if crops is None:
+            table = self.draw([(int(n.shape[0]), int(n.shape[1])) for n in ns])
+        else:
+            table = np.asarray(crops.cpu() if torch.is_tensor(crops) else crops)
+            assert table.shape == (B, P, 3), f"crops must be ({B},{P},3), got {table.shape}"
+            assert np.issubdtype(table.dtype, np.integer), "crops must be integers"
+            for b, n in enumerate(ns):
+                t = table[b]
+                if (t < 0).any() or (t[:, 0] > n.shape[0] - T).any() or (t[:, 1] > n.shape[1] - T).any() or (t[:, 2] > 7).any():
+                    raise VuError(f"crops[{b}] leaves the image ({n.shape[0]} x {n.shape[1]}, patch {T}) or names an op outside 0 .. 7")
+            table = np.ascontiguousarray(table, dtype=np.int32)
+        dev = ns[0].device
+        L, st = lib(), stream_ptr(dev)
+        d = torch.from_numpy(table).to(dev)
+        x = torch.empty(B * P, Cn, T, T, dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        for b in range(B):
+            H, W = int(ns[b].shape[0]), int(ns[b].shape[1])
+            check(L.vu_patch_pairs_u8(ptr(ns[b]), ptr(cs[b]), ptr(x[b * P:(b + 1) * P]), ptr(y[b * P:(b + 1) * P]), H, W, Cn, T,
+                                      ptr(d[b]), P, self.mean, self.std, st), "vu_patch_pairs_u8")
+        return {"x": x, "y": y}
+
 
 class SegmentationBatchTransform:
     """Device-side scaling / augmentation for SegmentationDataset batches (the reference leaves both
@@ -158,9 +251,9 @@ class DenoisingDataset(torch.utils.data.Dataset):
         self.img_names, self.augments = img_names, augments
         self.clean_folder, self.noisy_folder, self.im_size = clean_folder, noisy_folder, im_size
         self.read = read or _read_png_bgr
-        if augments is not None and not isinstance(augments, DenoisingBatchTransform):
+        if augments is not None and not isinstance(augments, (DenoisingBatchTransform, DenoisingPatchTransform)):
             raise TypeError("augments must be a DenoisingBatchTransform (the albumentations pipeline of "
-                            "run_denoising.py:52-59 runs on the device here) or None")
+                            "run_denoising.py:52-59 runs on the device here), a DenoisingPatchTransform or None")
 
     def __getitem__(self, idx):
         name = self.img_names[idx]
@@ -171,7 +264,10 @@ class DenoisingDataset(torch.utils.data.Dataset):
         return len(self.img_names)
 
     def transform(self, items) -> Dict[str, torch.Tensor]:
-        """A list of items -> one device batch {'x','y'} (B,3,im,im) float32."""
+        """A list of items -> one device batch {'x','y'} (B,3,im,im) float32 (a `DenoisingPatchTransform` takes all items at
+        once, whatever their sizes, and gives B * per_image patches)."""
+        if isinstance(self.augments, DenoisingPatchTransform):
+            return self.augments([np.asarray(it['x']) for it in items], [np.asarray(it['y']) for it in items])
         t = self.augments or DenoisingBatchTransform(im_size=self.im_size, train=False)
         return _batched(items, lambda xs, ys: t(np.stack(xs), np.stack(ys)))
 

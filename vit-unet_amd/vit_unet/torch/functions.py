@@ -64,11 +64,11 @@ def ssim(model, dataloader, device="cuda"):
     return np.concatenate(score) if score else np.zeros(0)
 
 
-def _tiled_scores(model, pairs, overlap, batch, score):
+def _tiled_scores(model, pairs, overlap, batch, score, ensemble=1):
     """Full-resolution metric over (noisy_u8, clean_u8) pairs of (H,W,C) images: the restorer's float image against clean / 255
     (what `DenoisingBatchTransform` gives the model as target), one (1,C,H,W) call of `score` per pair."""
     from .restore import TiledRestorer
-    r = TiledRestorer(model, overlap=overlap, batch=batch)
+    r = TiledRestorer(model, overlap=overlap, batch=batch, ensemble=ensemble)
     res = []
     for noisy, clean in pairs:
         out = r(noisy, output="f32")
@@ -79,15 +79,16 @@ def _tiled_scores(model, pairs, overlap, batch, score):
     return np.concatenate(res) if res else np.zeros(0)
 
 
-def psnr_tiled(model, pairs, overlap: int = 32, batch: int = 64):
+def psnr_tiled(model, pairs, overlap: int = 32, batch: int = 64, ensemble: int = 1):
     """`psnr` at full resolution: every pair of (H,W,C) uint8 images goes through sliding-window inference
-    (restore.TiledRestorer) instead of a resize to im_size.  Returns one value per pair."""
-    return _tiled_scores(model, pairs, overlap, batch, psnr_batch)
+    (restore.TiledRestorer, with its self-ensemble when `ensemble` > 1) instead of a resize to im_size.  Returns one
+    value per pair."""
+    return _tiled_scores(model, pairs, overlap, batch, psnr_batch, ensemble)
 
 
-def ssim_tiled(model, pairs, overlap: int = 32, batch: int = 64):
+def ssim_tiled(model, pairs, overlap: int = 32, batch: int = 64, ensemble: int = 1):
     """`ssim` at full resolution (see `psnr_tiled`)."""
-    return _tiled_scores(model, pairs, overlap, batch, ssim_batch)
+    return _tiled_scores(model, pairs, overlap, batch, ssim_batch, ensemble)
 
 
 class _Dice(torch.autograd.Function):

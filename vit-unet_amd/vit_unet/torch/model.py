@@ -692,14 +692,15 @@ class HViT_UNet(nn.Module):
             return _ModelFn.apply(X, self._anchor, self, training, seed)
         return self._run_forward(X, training, seed)
 
-    def restore(self, image, overlap: int = 32, batch: int = 64):
+    def restore(self, image, overlap: int = 32, batch: int = 64, ensemble: int = 1):
         """Restore a whole image of any size by sliding-window inference (restore.TiledRestorer, built once per
-        (overlap, batch) and kept).  `forward` is unchanged: it still resizes inputs of another size."""
+        (overlap, batch, ensemble) and kept; `ensemble` in {1, 2, 4, 8}: the self-ensemble over flips / rotations).
+        `forward` is unchanged: it still resizes inputs of another size."""
         from .restore import TiledRestorer
-        key = (int(overlap), int(batch))
+        key = (int(overlap), int(batch), ensemble)
         cache = self.__dict__.setdefault("_restorers", {})
         if key not in cache:
-            cache[key] = TiledRestorer(self, overlap=overlap, batch=batch)
+            cache[key] = TiledRestorer(self, overlap=overlap, batch=batch, ensemble=ensemble)
         return cache[key](image)
 
 

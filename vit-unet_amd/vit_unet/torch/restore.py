@@ -7,7 +7,9 @@ runs the model's eval forward on batches of windows and blends the window output
 H x W image with a separable ramp weight, normalised per pixel.  Cutting and blending are the HIP
 kernels of csrc/vu_tile.hip (C ABI `vu_tile_gather_u8` / `_f32`, `vu_tile_blend`; the plan and the
 weights are documented in include/vit_unet_amd.h); the model call in the middle is the unchanged
-`vu_model_forward` path.  No CPU fallback.
+`vu_model_forward` path.  `ensemble=K` is the self-ensemble: every window is restored under K of the
+eight flips / rotations of the square and the K results, turned back, are averaged before the blend
+(csrc/vu_patch.hip, C ABI `vu_dihedral_f32`).  No CPU fallback.
 """
 from __future__ import annotations
 
@@ -46,9 +48,16 @@ class TiledRestorer:
 
     The eval forward (running BatchNorm statistics, no dropout) runs under `torch.no_grad()` whatever mode the model is
     in; neither the mode nor the running statistics are touched.  Windows run in chunks of `batch`, the last chunk at
-    its own size; all window outputs of one image are kept (nt C T^2 floats) and blended in one launch."""
+    its own size; all window outputs of one image are kept (nt C T^2 floats) and blended in one launch.
 
-    def __init__(self, model, overlap: int = 32, batch: int = 64, mean: float = 0.456, std: float = 0.224):
+    `ensemble` in {1, 2, 4, 8}: the dihedral ops (0,), (0, 4), (0, 1, 2, 3), (0 .. 7) (op & 3 counter-clockwise quarter
+    turns after a left-right flip when op & 4).  Per chunk and op, in this order: transform the windows, run the eval
+    forward, add the output under the inverse op to the chunk's slot (the first op stores, the last one also scales by
+    1 / K).  K forwards and 2 K transform launches per chunk; `ensemble=1` launches none of them and is today's path."""
+
+    ENSEMBLE_OPS = {1: (0,), 2: (0, 4), 4: (0, 1, 2, 3), 8: (0, 1, 2, 3, 4, 5, 6, 7)}
+
+    def __init__(self, model, overlap: int = 32, batch: int = 64, mean: float = 0.456, std: float = 0.224, ensemble: int = 1):
         T = int(model.im_size)
         if not 0 <= int(overlap) <= T // 2:
             raise VuError(f"overlap must be in 0 .. im_size // 2 = {T // 2} (got {overlap})")
@@ -57,7 +66,9 @@ class TiledRestorer:
         if not float(std) > 0:
             raise VuError(f"std must be positive (got {std})")
         self.model, self.T, self.overlap, self.batch = model, T, int(overlap), int(batch)
-        self.mean, self.std = float(mean), float(std)
+        if ensemble not in self.ENSEMBLE_OPS:
+            raise VuError(f"ensemble must be one of {sorted(self.ENSEMBLE_OPS)} (got {ensemble!r})")
+        self.mean, self.std, self.ensemble = float(mean), float(std), int(ensemble)
 
     def _device(self) -> torch.device:
         dev = next(self.model.parameters()).device
@@ -101,13 +112,23 @@ class TiledRestorer:
         m._ensure_flat()
         outs = torch.empty(nt, Cn, T, T, dtype=torch.float32, device=dev)
         x = torch.empty(min(self.batch, nt), Cn, T, T, dtype=torch.float32, device=dev)
+        ops = self.ENSEMBLE_OPS[self.ensemble]
+        if len(ops) > 1:
+            xt, scratch = torch.empty_like(x), torch.empty_like(x)
         for t0 in range(0, nt, self.batch):
             n = min(self.batch, nt - t0)
             if img.dtype == torch.uint8:
                 check(L.vu_tile_gather_u8(ptr(img), ptr(x), H, W, Cn, T, ov, t0, n, self.mean, self.std, st), "vu_tile_gather_u8")
             else:
                 check(L.vu_tile_gather_f32(ptr(img), ptr(x), H, W, Cn, T, ov, t0, n, st), "vu_tile_gather_f32")
-            m._run_forward(x[:n], False, 0, out=outs[t0:t0 + n])
+            if len(ops) == 1:
+                m._run_forward(x[:n], False, 0, out=outs[t0:t0 + n])
+                continue
+            for k, op in enumerate(ops):
+                check(L.vu_dihedral_f32(ptr(x), ptr(xt), n, Cn, T, op, 0, 1.0, st), "vu_dihedral_f32")
+                m._run_forward(xt[:n], False, 0, out=scratch[:n])
+                check(L.vu_dihedral_f32(ptr(scratch), ptr(outs[t0:t0 + n]), n, Cn, T, L.vu_dihedral_inverse(op), int(k > 0),
+                                        1.0 / len(ops) if k == len(ops) - 1 else 1.0, st), "vu_dihedral_f32")
         if output == "u8":
             res = torch.empty(H, W, Cn, dtype=torch.uint8, device=dev)
             check(L.vu_tile_blend(ptr(outs), None, ptr(res), H, W, Cn, T, ov, st), "vu_tile_blend")

@@ -3,7 +3,10 @@ decoding (those stay with the caller) - per fold: build the preset model, `AdamW
 `fit(train, val, n_epochs, callbacks)`, reload `best-checkpoint.bin`, per-image PSNR of the test
 split.  The loaders feed decoded uint8 HWC images through the device-side input pipeline
 (`dataset.DenoisingBatchTransform`: train transform on the training split, validation transform on
-the test split, run_denoising.py:52-59)."""
+the test split, run_denoising.py:52-59).  `patch_train=True` is the native-resolution recipe instead:
+random crops under flips / rotations for training (`dataset.DenoisingPatchTransform`), a centred crop
+for the validation loss, and the per-fold score from whole test images through sliding-window inference
+(`functions.psnr_tiled`, with its self-ensemble when `ensemble` > 1)."""
 from __future__ import annotations
 
 import os
@@ -14,7 +17,7 @@ import torch
 
 from . import functions as fn
 from . import model as models
-from .dataset import DenoisingBatchTransform, ImageFitter
+from .dataset import DenoisingBatchTransform, DenoisingPatchTransform, ImageFitter
 
 
 def kfold_indices(n: int, folds: int, seed: Optional[int] = None):
@@ -54,17 +57,28 @@ class BatchLoader:
 def run_denoising(noisy: np.ndarray, clean: np.ndarray, n_epochs: int = 5, folds: int = 5, model_string: str = "lite",
                   lr: float = 1e-4, batch_size: int = 8, im_size: int = 224, folder: str = "models", seed: int = 0,
                   dtype=torch.bfloat16, callbacks: Optional[List[Callable[[int, Dict], None]]] = None,
-                  verbose: bool = False) -> Dict:
+                  verbose: bool = False, patch_train: bool = False, crops_per_image: int = 8, ensemble: int = 1) -> Dict:
     """noisy / clean: (n,H,W,3) uint8 decoded images (what `cv2.imread` returns for the SIDD pairs).
-    Returns {'psnr': [per-fold arrays], 'psnr_mean', 'psnr_std', 'history'} (run_denoising.py:113-119)."""
+    Returns {'psnr': [per-fold arrays], 'psnr_mean', 'psnr_std', 'history'} (run_denoising.py:113-119).
+    `patch_train`: train on `crops_per_image` random im_size patches per image at native resolution (`batch_size` then
+    counts patches: batch_size // crops_per_image images per step) and score whole images with `psnr_tiled(ensemble=)`."""
     assert len(clean) == len(noisy), f"Clean length {len(clean)} is not equal to Noisy length {len(noisy)}"
+    if patch_train:
+        assert crops_per_image >= 1 and batch_size % crops_per_image == 0, \
+            f"batch_size {batch_size} (patches) must be a multiple of crops_per_image {crops_per_image}"
     results, histories = [], []
     for fold, (train_idx, test_idx) in enumerate(kfold_indices(len(noisy), folds, seed)):
         if verbose:
             print(f"FOLD {fold}: Training on {len(train_idx)} samples and testing on {len(test_idx)} samples")
-        train = BatchLoader(noisy, clean, train_idx, batch_size, DenoisingBatchTransform(im_size, train=True, seed=seed + fold),
-                            shuffle=True, seed=seed + fold)
-        test = BatchLoader(noisy, clean, test_idx, batch_size, DenoisingBatchTransform(im_size, train=False), shuffle=False)
+        if patch_train:
+            train = BatchLoader(noisy, clean, train_idx, batch_size // crops_per_image,
+                                DenoisingPatchTransform(im_size, crops_per_image, train=True, seed=seed + fold), shuffle=True,
+                                seed=seed + fold)
+            test = BatchLoader(noisy, clean, test_idx, batch_size, DenoisingPatchTransform(im_size, train=False), shuffle=False)
+        else:
+            train = BatchLoader(noisy, clean, train_idx, batch_size, DenoisingBatchTransform(im_size, train=True, seed=seed + fold),
+                                shuffle=True, seed=seed + fold)
+            test = BatchLoader(noisy, clean, test_idx, batch_size, DenoisingBatchTransform(im_size, train=False), shuffle=False)
         model = models.get_vit_unet(model_string, dtype=dtype)
         model.to("cuda")
         criterion = torch.nn.MSELoss()
@@ -75,7 +89,10 @@ def run_denoising(noisy: np.ndarray, clean: np.ndarray, n_epochs: int = 5, folds
         fitter.load(os.path.join(folder, "best-checkpoint.bin"))
         model = fitter.model
         model.eval()
-        score = fn.psnr(model, test)
+        if patch_train:
+            score = fn.psnr_tiled(model, ((noisy[i], clean[i]) for i in test_idx), overlap=min(32, im_size // 2), ensemble=ensemble)
+        else:
+            score = fn.psnr(model, test)
         if verbose:
             print(f"FOLD {fold}: Mean PSNR {np.mean(score)}")
         results.append(score)
