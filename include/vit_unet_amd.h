@@ -290,6 +290,30 @@ int vu_tile_gather_u8(const uint8_t* img, float* tiles, int H, int W, int C, int
 int vu_tile_gather_f32(const float* img, float* tiles, int H, int W, int C, int T, int overlap, int t0, int n, void* stream);
 int vu_tile_blend(const float* tiles, float* out_f32, uint8_t* out_u8, int H, int W, int C, int T, int overlap, void* stream);
 
+/* Whole-slice / volume segmentation (csrc/vu_segtile.hip; no reference counterpart): the same sliding-window inference for the
+ * 1-channel segmentation configuration.  vol is (D,H,W) int16 (one slice: D = 1); every slice has the plan above (nt = ny nx windows)
+ * and windows are numbered over the whole volume, g = z nt + t.
+ *   gather_i16   windows [g0, g0 + n) (the range may cross slice boundaries) as tiles (n,1,T,T) float32: the crop, inward shift and
+ *                reflection of gather_f32, values under the intensity window of the seg-prepare call above,
+ *                x = clip((v - lo) / (hi - lo), 0, 1) (hi - lo in float32; bit for bit what seg-prepare gives the same pixels without
+ *                resize and warp).  Refused: hi <= lo, null pointers, a range outside D nt.
+ *   seg_blend    tiles (nz nt,1,T,T) float32, the model outputs (logits) for the WHOLE plan of nz consecutive slices.  Per pixel z is the
+ *                blended logit with exactly the arithmetic of vu_tile_blend at C = 1 (bit-identical to its out_f32, slice by slice);
+ *                  logits (nz,H,W) float32 = z        mask (nz,H,W) uint8 = z >= zthr ? 1 : 0
+ *                  counts (nz,3) uint64 per slice: mask pixels, truth pixels, pixels where both are set; a truth pixel is
+ *                  truth != 0 when label < 0 and truth == label when 0 <= label <= 255 (truth: (nz,H,W) uint8).
+ *                logits, mask and counts may each be NULL, not all three; counts needs truth (refused otherwise; truth without counts
+ *                is not read) and scratch >= vu_seg_blend_scratch_bytes(nz, H, W), 4-byte aligned (per-block partial counts, summed
+ *                per slice in a fixed order by a second launch: exact integers whatever the launch geometry, no atomics).  The
+ *                outputs must not alias `tiles`.  A probability threshold thr in (0,1) is zthr = log(thr / (1 - thr)) (0 for 0.5);
+ *                the probability itself is not an output (sigmoid of `logits`).
+ * T % 4 == 0 and aligned buffers take 8-byte int16 loads, 16-byte float and 4-byte mask / truth accesses; anything else is scalar. */
+int vu_tile_gather_i16(const int16_t* vol, float* tiles, int D, int H, int W, int T, int overlap, long long g0, int n, float lo,
+                       float hi, void* stream);
+size_t vu_seg_blend_scratch_bytes(int nz, int H, int W);
+int vu_seg_blend(const float* tiles, const uint8_t* truth, float* logits, uint8_t* mask, unsigned long long* counts, void* scratch,
+                 size_t scratch_bytes, int nz, int H, int W, int T, int overlap, float zthr, int label, void* stream);
+
 /* Native-resolution training patches and the self-ensemble (csrc/vu_patch.hip; no reference counterpart).  Both rest on the dihedral
  * transforms of a T x T window: op in 0 .. 7, k = op & 3 counter-clockwise quarter turns applied after a left-right flip when op & 4,
  *   D_op(p) = np.rot90(np.fliplr(p) if op & 4 else p, k = op & 3),   m = flipped or plain p with m[a,b] = p[a, T-1-b]:

@@ -13,3 +13,9 @@ __device__ __forceinline__ float vu_normalize_u8(int v, float m255, float rden) 
 }
 // the clean image is divided as uint8/255. (float64) and cast to float32 by unpack (dataset.py:66,80)
 __device__ __forceinline__ float vu_unit_u8(int v) { return (float)__ddiv_rn((double)v, 255.0); }
+
+// the intensity window of the segmentation input pipeline (vu_seg_prepare, and vu_tile_gather_i16 of csrc/vu_segtile.hip):
+// x = clip((v - lo) / range, 0, 1) with range = hi - lo in float32, every operation rounded once
+__device__ __forceinline__ float vu_window_i16(int v, float lo, float range) {
+  return fminf(fmaxf(__fdiv_rn(__fsub_rn((float)v, lo), range), 0.f), 1.f);
+}

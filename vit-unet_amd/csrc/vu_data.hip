@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void warp_seg_kernel(const int16_t* __restrict
     if (img) vi = img[base + p];
     if (mask) vm = mask[base + p];
   }
-  if (img) x[base + p] = fminf(fmaxf(__fdiv_rn(__fsub_rn((float)vi, lo), range), 0.f), 1.f);
+  if (img) x[base + p] = vu_window_i16(vi, lo, range);
   if (mask) y[base + p] = __fadd_rn(__fmul_rn((float)vm, keep), floor_);
 }
 

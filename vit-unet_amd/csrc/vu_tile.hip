@@ -17,46 +17,10 @@
 // plan order - no atomics, no dependence on the launch geometry, the same bits on every run.
 #include "vu_common.h"
 #include "vu_data.h"
+#include "vu_tile_plan.h"
 #include "../../include/vit_unet_amd.h"
 
 namespace {
-
-struct tile_axis {
-  int L, T, S, ov, n;
-};
-
-inline int axis_count(int L, int T, int S) { return L <= T ? 1 : (int)vu_cdiv64((long long)L - T, S) + 1; }
-
-inline tile_axis make_axis(int L, int T, int overlap) {
-  tile_axis a;
-  a.L = L; a.T = T; a.ov = overlap; a.S = T - overlap;
-  a.n = axis_count(L, T, a.S);
-  return a;
-}
-
-__host__ __device__ __forceinline__ int axis_origin(const tile_axis& a, int i) {
-  const int r = i * a.S, last = a.L - a.T;
-  return a.L <= a.T ? 0 : (r < last ? r : last);
-}
-
-// the first window (in plan order) that covers pixel p; the ones after it cover p while their origin is <= p
-__device__ __forceinline__ int axis_first(const tile_axis& a, int p) {
-  if (a.L <= a.T || p < a.T) return 0;
-  return min((p - a.T) / a.S + 1, a.n - 1);
-}
-
-// source index of window position k = origin + i: the pixel itself, or (L < T only) its reflection without the edge
-__device__ __forceinline__ int axis_src(const tile_axis& a, int k) {
-  if (k < a.L) return k;
-  if (a.L == 1) return 0;
-  const int m = 2 * (a.L - 1);
-  k %= m;
-  return k < a.L ? k : m - k;
-}
-
-__device__ __forceinline__ float axis_weight(const tile_axis& a, int i) {
-  return __fdiv_rn((float)min(min(i + 1, a.T - i), a.ov + 1), (float)(a.ov + 1));
-}
 
 // one thread = 4 consecutive columns of one row of one window, all channels: CH bytes per pixel in, CH float4 out
 template <int CH>
@@ -228,13 +192,6 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict
           for (int c = 0; c < CH; ++c) out_u8[o + j * CH + c] = b[j * CH + c];
     }
   }
-}
-
-int check_plan(const char* who, int H, int W, int T, int overlap) {
-  VU_REQUIRE(T > 0, "%s: the window size must be positive (got %d)", who, T);
-  VU_REQUIRE(H > 0 && W > 0, "%s: empty image (%d x %d)", who, H, W);
-  VU_REQUIRE(overlap >= 0 && overlap <= T / 2, "%s: overlap must be in 0 .. T/2 = %d (got %d)", who, T / 2, overlap);
-  return VU_OK;
 }
 
 int check_range(const char* who, const tile_axis& Y, const tile_axis& X, int C, int t0, int n) {

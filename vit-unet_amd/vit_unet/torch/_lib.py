@@ -119,6 +119,9 @@ SIGNATURES = {
     "vu_tile_gather_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "vu_tile_gather_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "vu_tile_blend": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vu_tile_gather_i16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _i, _f, _f, _vp]),
+    "vu_seg_blend_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vu_seg_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "vu_dihedral_inverse": (_i, [_i]),
     "vu_patch_pairs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _vp]),
     "vu_dihedral_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

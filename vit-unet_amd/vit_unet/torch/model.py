@@ -703,6 +703,17 @@ class HViT_UNet(nn.Module):
             cache[key] = TiledRestorer(self, overlap=overlap, batch=batch, ensemble=ensemble)
         return cache[key](image)
 
+    def segment(self, vol, output: str = "mask", **kw):
+        """Label mask of a whole int16 slice (H,W) or volume (D,H,W) of any size by sliding-window inference
+        (segment.TiledSegmenter, built once per set of its keyword arguments - overlap, batch, window, threshold, label,
+        ensemble - and kept).  `forward` is unchanged: it still resizes inputs of another size."""
+        from .segment import TiledSegmenter
+        key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items()))
+        cache = self.__dict__.setdefault("_segmenters", {})
+        if key not in cache:
+            cache[key] = TiledSegmenter(self, **kw)
+        return cache[key](vol, output)
+
 
 def ViT_UNet(depth, depth_te, size_bottleneck, preprocessing, num_patches, patch_size, num_channels=3,
              hidden_dim=128, num_heads=8, attn_drop=0., proj_drop=0., linear_drop=0., dtype=torch.float32,
