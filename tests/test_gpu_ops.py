@@ -288,6 +288,7 @@ def test_gemm_batched_heads(dt):
     kh = k.double().view(B, N, H, d).permute(0, 2, 1, 3)
     ref = qh @ kh.transpose(-1, -2) * d ** -0.5
     assert serr(S[..., :N], ref) < ft * 40
+    assert bool((S[..., N:] == 0).all())                               # the padding columns (ldc = 56 > N) are not written
     A = torch.randn(B, H, N, ld, generator=g).to(dt)
     out = torch.zeros(B, N, D, dtype=dt, device=DEV)
     _gemm(dt, dev(A), dev(k), N, d, N, ld, 1, D, 1, Z1=B, Z2=H, sA=(H * N * ld, N * ld), sB=(N * D, d), sC=(N * D, d), ldc=D, out=out)
