@@ -334,6 +334,48 @@ int vu_patch_pairs_u8(const uint8_t* noisy, const uint8_t* clean, float* x, floa
                       int n, float mean, float std, void* stream);
 int vu_dihedral_f32(const float* src, float* dst, int n, int C, int T, int op, int accumulate, float scale, void* stream);
 
+/* Native-resolution segmentation training patches with foreground sampling (csrc/vu_segpatch.hip; no reference counterpart): the
+ * int16 / label-mask twin of the patch call above.  vol is (D,H,W) int16, mask (D,H,W) uint8 (one slice: D = 1); a crop is a T x T
+ * window of ONE slice.  A foreground pixel is mask != 0 when label < 0 and mask == label when 0 <= label <= 255 (the truth rule of the
+ * seg-blend call above).  Everywhere: D H W < 2^32, label <= 255.  All index arithmetic is integer:
+ *   fg_index     index (D H + 1) uint32: index[r] = number of foreground pixels in rows [0, r) of the volume taken as D H rows of W
+ *                pixels (row q = slice q / H, line q % H), so index[0] = 0 and index[D H] = total.  scratch >= vu_fg_index_bytes(D, H),
+ *                4-byte aligned (row counts and the chunk totals of a scan with a fixed geometry: integers, no atomics, the same bits
+ *                on every run).  W % 4 == 0 and a 4-byte aligned mask take 4-byte mask loads, anything else byte loads.
+ *   draw         rnd (n,4) uint32 and crops (n,4) int32 (z, y0, x0, op), both in DEVICE memory and 16-byte aligned; index as above
+ *                (of the same mask and label).  T <= H, W <= 65535.  With total = index[D H], per crop i:
+ *                  foreground crop, when rnd[i,0] < fg_thresh and total > 0:
+ *                    r = (uint64(rnd[i,1]) * total) >> 32          the r-th foreground pixel in raster order over the volume:
+ *                    q = the row with index[q] <= r < index[q+1],   z = q / H,  y = q % H,
+ *                    x = the column of the (r - index[q])-th foreground pixel of that row (counted from 0)
+ *                    oy = ((rnd[i,2] >> 16) * T) >> 16,            ox = ((rnd[i,2] & 0xffff) * T) >> 16
+ *                    y0 = clamp(y - oy, 0, H - T),                 x0 = clamp(x - ox, 0, W - T)
+ *                  (so the pixel lies inside the crop); otherwise:
+ *                    z  = (uint64(rnd[i,1]) * D) >> 32
+ *                    y0 = ((rnd[i,2] >> 16) * (H - T + 1)) >> 16,  x0 = ((rnd[i,2] & 0xffff) * (W - T + 1)) >> 16
+ *                  in both cases op = rnd[i,3] & 7.
+ *                fg_thresh = 0 never samples foreground; the total is read on the device: no host synchronisation.  An index that
+ *                does not belong to the mask cannot make the kernel read outside either buffer (the search is bounded, the walk of a
+ *                row ends at x = W - 1).
+ *   patch_pairs_i16  crops (n,4) int32 (z, y0, x0, op) in DEVICE memory, 16-byte aligned.  With p = the crop [z, y0:y0+T, x0:x0+T]:
+ *                  x[i] = D_op(clip((vol p - lo) / (hi - lo), 0, 1))   the intensity window of the seg-prepare call (hi - lo in float32,
+ *                         every operation rounded once): the bits seg-prepare and gather_i16 give the same pixels
+ *                  y[i] = D_op(t * (1 - ls) + ls / 2),  t = 1 on a foreground pixel of mask p, else 0 (float32: keep = 1 - ls and
+ *                         floor = 0.5 ls are formed first, then one product and one sum, as seg-prepare does; for a {0,1} mask and
+ *                         label < 0 bit for bit what seg-prepare gives without resize and warp)
+ *                both (n,1,T,T) float32, D_op as defined above.  A pair may be omitted (vol == x == NULL or mask == y == NULL).
+ *                The KERNEL CLAMPS the table: z to [0, D-1], y0 to [0, H-T], x0 to [0, W-T], op to op & 7.
+ * Refused before any launch: null or inconsistent pointers, hi <= lo, ls outside [0,1), label > 255, H < T or W < T, n < 1, T < 1,
+ * the size limits above, a short or misaligned scratch.  T % 4 == 0 and 16-byte aligned outputs take 16-byte stores, anything else
+ * scalar ones. */
+size_t vu_fg_index_bytes(int D, int H);
+int vu_fg_index(const uint8_t* mask, uint32_t* index, void* scratch, size_t scratch_bytes, int D, int H, int W, int label,
+                void* stream);
+int vu_segpatch_draw(const uint8_t* mask, const uint32_t* index, const uint32_t* rnd, int* crops, int n, int D, int H, int W, int T,
+                     uint32_t fg_thresh, int label, void* stream);
+int vu_patch_pairs_i16(const int16_t* vol, const uint8_t* mask, float* x, float* y, int D, int H, int W, int T, const int* crops, int n,
+                       float lo, float hi, float ls, int label, void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

@@ -125,6 +125,10 @@ SIGNATURES = {
     "vu_dihedral_inverse": (_i, [_i]),
     "vu_patch_pairs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _vp]),
     "vu_dihedral_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "vu_fg_index_bytes": (_sz, [_i, _i]),
+    "vu_fg_index": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "vu_segpatch_draw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_uint32, _i, _vp]),
+    "vu_patch_pairs_i16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _f, _i, _vp]),
     "vu_add": (_i, [_i, _vp, _vp, _vp, _ll, _vp]),
     "vu_dropout": (_i, [_i, _vp, _vp, _ll, _f, _u64, _u64, _vp]),
     "vu_gelu_fwd": (_i, [_i, _vp, _vp, _ll, _vp]),

@@ -9,6 +9,8 @@ for the whole batch with the HIP kernels of csrc/vu_data.hip (C ABI `vu_denoise_
 returns the `{'x','y'}` dict `ImageFitter.unpack` expects.  `DenoisingPatchTransform` is the
 native-resolution recipe instead of the resize: random aligned crops of the pair, each under one
 of the eight flips / rotations of the square (csrc/vu_patch.hip, C ABI `vu_patch_pairs_u8`).
+`SegmentationPatchTransform` is the same recipe for int16 volumes and their label masks, with crops drawn on the
+device so that a chosen share holds foreground (csrc/vu_segpatch.hip).
 No CPU fallback.
 """
 from __future__ import annotations
@@ -230,6 +232,129 @@ class SegmentationBatchTransform:
         return out
 
 
+class SegmentationPatchTransform:
+    """Native-resolution segmentation training patches: `per_volume` crops of `patch` x `patch` pixels of single slices out
+    of every int16 volume and its uint8 label mask, each under one of the eight dihedral ops of `DenoisingPatchTransform`,
+    the slice under the intensity window `window` and the mask as label (1 - ls) + ls / 2 exactly as
+    `SegmentationBatchTransform(train=False)` gives them - no resize anywhere.  A foreground pixel is mask != 0 (`label` < 0)
+    or mask == label.  Call with `(image, mask)`: one (H,W) / (D,H,W) int16 volume and its uint8 mask, or lists of them whose
+    sizes may differ (numpy or torch, host or device); returns {'x','y'} (sum per_volume,1,patch,patch) float32 on the device,
+    the patches of volume 0 first.
+
+    `train=True`: the crops are drawn ON THE DEVICE (C ABI `vu_fg_index`, `vu_segpatch_draw`) from `draw_words(per_volume)`,
+    four uint32 words per crop out of the transform's own `random.Random(seed)`: with probability `fg` a crop is placed
+    around a uniformly chosen foreground pixel of the volume (which then lies inside it), otherwise (and when the volume has
+    no foreground) uniformly; the formulas are in include/vit_unet_amd.h.  The host never waits for the device.
+    `train=False` is ONE centred crop of the middle slice (z = D//2, y0 = (H-T)//2, x0 = (W-T)//2) with op 0 and launches no
+    draw.  `crops=` - one (per_volume,4) integer table (z, y0, x0, op) per volume - replaces the draw and is checked on the
+    host.  `last_crops` keeps the device tables of the last call (a list, one (per_volume,4) int32 tensor per volume).
+    Argument errors raise `VuError` before any launch (the cut itself clamps what it is given)."""
+
+    def __init__(self, patch: int = 224, per_volume: int = 8, train: bool = True, window=(-1024.0, 1024.0), ls: float = 0.0,
+                 fg: float = 0.5, label: int = -1, device="cuda", seed: Optional[int] = None):
+        self.patch, self.train = int(patch), bool(train)
+        self.per_volume = int(per_volume) if self.train else 1
+        if self.patch < 1 or self.per_volume < 1:
+            raise VuError(f"patch and per_volume must be at least 1 (got {patch}, {per_volume})")
+        if self.patch > 65535:
+            raise VuError(f"a patch has at most 65535 pixels a side (got {patch})")
+        lo, hi = float(np.float32(window[0])), float(np.float32(window[1]))
+        if not hi > lo:
+            raise VuError(f"the intensity window must have hi > lo (got {window[0]} .. {window[1]})")
+        if not 0.0 <= float(ls) < 1.0:
+            raise VuError(f"label smoothing must be in [0,1) (got {ls})")
+        if not 0.0 <= float(fg) <= 1.0:
+            raise VuError(f"fg, the share of foreground crops, must be in [0,1] (got {fg})")
+        if int(label) > 255:
+            raise VuError(f"label must be negative (any non-zero mask value) or 0 .. 255 (got {label})")
+        self.window, self.ls, self.fg, self.label, self.device = (lo, hi), float(ls), float(fg), int(label), device
+        self.rng = random.Random(seed)
+        self.last_crops: Optional[List[torch.Tensor]] = None
+
+    @property
+    def fg_thresh(self) -> int:
+        """A crop is a foreground crop when its first random word is below this (0: never)."""
+        return min(int(self.fg * 2 ** 32), 2 ** 32 - 1)
+
+    def draw_words(self, n: int) -> np.ndarray:
+        """The next (n,4) uint32 words of the transform's generator (host code, no GPU): per crop the branch word, the rank /
+        slice word, the two 16-bit offsets and the op word."""
+        return np.array([[self.rng.getrandbits(32) for _ in range(4)] for _ in range(int(n))], dtype=np.uint32).reshape(int(n), 4)
+
+    def _volumes(self, a, dtype, what) -> List[torch.Tensor]:
+        if isinstance(a, np.ndarray) or torch.is_tensor(a):
+            a = [a]
+        if not isinstance(a, (list, tuple)) or len(a) == 0:
+            raise VuError(f"expected one (H,W) or (D,H,W) {dtype} {what} or a non-empty list of them")
+        out = []
+        for v in a:
+            t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v
+            if not torch.is_tensor(t) or t.dim() not in (2, 3) or t.dtype != dtype or t.numel() == 0:
+                got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(v).__name__
+                raise VuError(f"expected (H,W) or (D,H,W) {dtype} {what}s, got {got}")
+            out.append(t.reshape((-1,) + tuple(t.shape[-2:])))
+        return out
+
+    def _check_table(self, crops, b, shape) -> np.ndarray:
+        D, H, W = shape
+        T, P = self.patch, self.per_volume
+        t = np.asarray(crops.cpu() if torch.is_tensor(crops) else crops)
+        if t.shape != (P, 4) or not np.issubdtype(t.dtype, np.integer):
+            raise VuError(f"crops[{b}] must be an integer table of shape ({P},4), got {t.dtype} {t.shape}")
+        if (t < 0).any() or (t[:, 0] > D - 1).any() or (t[:, 1] > H - T).any() or (t[:, 2] > W - T).any() or (t[:, 3] > 7).any():
+            raise VuError(f"crops[{b}] leaves the volume ({D} x {H} x {W}, patch {T}) or names an op outside 0 .. 7")
+        return np.ascontiguousarray(t, dtype=np.int32)
+
+    def __call__(self, image, mask, crops=None) -> Dict[str, torch.Tensor]:
+        vs, ms = self._volumes(image, torch.int16, "volume"), self._volumes(mask, torch.uint8, "mask")
+        if len(vs) != len(ms):
+            raise VuError(f"{len(vs)} volumes and {len(ms)} masks")
+        T, P, B = self.patch, self.per_volume, len(vs)
+        shapes = []
+        for b, (v, m) in enumerate(zip(vs, ms)):
+            if v.shape != m.shape:
+                raise VuError(f"pair {b}: volume {tuple(v.shape)} and mask {tuple(m.shape)} differ")
+            D, H, W = (int(s) for s in v.shape)
+            if H < T or W < T:
+                raise VuError(f"volume {b} ({H} x {W} slices) is smaller than a patch of {T}")
+            if H > 65535 or W > 65535 or D * H * W >= 2 ** 32:
+                raise VuError(f"volume {b} ({D} x {H} x {W}) is too large (65535 a side, below 2^32 pixels)")
+            shapes.append((D, H, W))
+        tables = None
+        if crops is not None:
+            if len(crops) != B:
+                raise VuError(f"crops must hold one ({P},4) table per volume ({B}), got {len(crops)}")
+            tables = [self._check_table(c, b, shapes[b]) for b, c in enumerate(crops)]
+        elif not self.train:
+            tables = [np.array([[D // 2, (H - T) // 2, (W - T) // 2, 0]], dtype=np.int32) for D, H, W in shapes]
+        if not str(self.device).startswith("cuda"):
+            raise VuError("SegmentationPatchTransform runs on the MI355X only (device 'cuda'; no CPU fallback)")
+        vs = [v.to(self.device, non_blocking=True).contiguous() for v in vs]
+        ms = [m.to(self.device, non_blocking=True).contiguous() for m in ms]
+        dev = vs[0].device
+        L, st = lib(), stream_ptr(dev)
+        lo, hi = self.window
+        x = torch.empty(B * P, 1, T, T, dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        self.last_crops = []
+        for b, (D, H, W) in enumerate(shapes):
+            if tables is not None:
+                d = torch.from_numpy(tables[b]).to(dev)
+            else:
+                words = torch.from_numpy(self.draw_words(P).view(np.int32)).to(dev)
+                index = torch.empty(D * H + 1, dtype=torch.int32, device=dev)
+                nbytes = int(L.vu_fg_index_bytes(D, H))
+                scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+                d = torch.empty(P, 4, dtype=torch.int32, device=dev)
+                check(L.vu_fg_index(ptr(ms[b]), ptr(index), ptr(scratch), nbytes, D, H, W, self.label, st), "vu_fg_index")
+                check(L.vu_segpatch_draw(ptr(ms[b]), ptr(index), ptr(words), ptr(d), P, D, H, W, T, self.fg_thresh, self.label, st),
+                      "vu_segpatch_draw")
+            self.last_crops.append(d)
+            check(L.vu_patch_pairs_i16(ptr(vs[b]), ptr(ms[b]), ptr(x[b * P:(b + 1) * P]), ptr(y[b * P:(b + 1) * P]), D, H, W, T, ptr(d),
+                                       P, lo, hi, self.ls, self.label, st), "vu_patch_pairs_i16")
+        return {"x": x, "y": y}
+
+
 def _read_png_bgr(path: str) -> np.ndarray:
     """cv2.imread(path) without OpenCV: decoded 8-bit pixels, HWC, BGR channel order."""
     from PIL import Image
@@ -277,15 +402,16 @@ class SegmentationDataset(torch.utils.data.Dataset):
     (H,W) uint8 labels} as read (`read_image(path)` / `read_mask(path, index)`; defaults: pydicom
     pixel_array and nibabel get_fdata()[:, :, index], imported lazily).  Scaling / augmentation runs
     per batch on the GPU: `augments` is a `SegmentationBatchTransform` (default: resize to `im_size`,
-    label smoothing `ls`, no warp).  `is_test`: items carry no mask."""
+    label smoothing `ls`, no warp) or a `SegmentationPatchTransform` (native-resolution crops with foreground
+    sampling; it needs the masks, so not with `is_test`).  `is_test`: items carry no mask."""
 
     def __init__(self, df, augments=None, is_test=False, data_folder='output', im_size=(128, 128), ls=0.0,
                  read_image=None, read_mask=None):
         self.df, self.augments, self.is_test = df, augments, is_test
         self.data_folder, self.im_size, self.ls = data_folder, im_size, ls
         self.read_image, self.read_mask = read_image or self._dicom, read_mask or self._nifti
-        if augments is not None and not isinstance(augments, SegmentationBatchTransform):
-            raise TypeError("augments must be a SegmentationBatchTransform or None")
+        if augments is not None and not isinstance(augments, (SegmentationBatchTransform, SegmentationPatchTransform)):
+            raise TypeError("augments must be a SegmentationBatchTransform, a SegmentationPatchTransform or None")
 
     @staticmethod
     def _dicom(path):
@@ -314,6 +440,12 @@ class SegmentationDataset(torch.utils.data.Dataset):
         return len(self.df)
 
     def transform(self, items) -> Dict[str, torch.Tensor]:
+        """A list of items -> one device batch (a `SegmentationPatchTransform` takes all items at once, whatever their sizes,
+        and gives len(items) * per_volume patches)."""
+        if isinstance(self.augments, SegmentationPatchTransform):
+            if self.is_test:
+                raise VuError("a SegmentationPatchTransform draws its crops from the masks: not with is_test")
+            return self.augments([np.asarray(it['x']) for it in items], [np.asarray(it['y']) for it in items])
         t = self.augments or SegmentationBatchTransform(im_size=self.im_size, train=False, ls=self.ls)
         if self.is_test:
             return _batched(items, lambda xs, ys: t(np.stack(xs), None), with_y=False)

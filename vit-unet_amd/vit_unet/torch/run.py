@@ -6,7 +6,12 @@ split.  The loaders feed decoded uint8 HWC images through the device-side input 
 the test split, run_denoising.py:52-59).  `patch_train=True` is the native-resolution recipe instead:
 random crops under flips / rotations for training (`dataset.DenoisingPatchTransform`), a centred crop
 for the validation loss, and the per-fold score from whole test images through sliding-window inference
-(`functions.psnr_tiled`, with its self-ensemble when `ensemble` > 1)."""
+(`functions.psnr_tiled`, with its self-ensemble when `ensemble` > 1).
+
+`run_segmentation` is the same loop for the 1-channel segmentation configuration, at native resolution throughout:
+K-fold over int16 volumes, training patches with foreground sampling (`dataset.SegmentationPatchTransform`), the fused
+Dice step (`ImageFitter(model, loss=DiceLoss())`), the validation loss on centred crops and the per-fold score from whole
+test volumes (`functions.dice_tiled`)."""
 from __future__ import annotations
 
 import os
@@ -17,7 +22,7 @@ import torch
 
 from . import functions as fn
 from . import model as models
-from .dataset import DenoisingBatchTransform, DenoisingPatchTransform, ImageFitter
+from .dataset import DenoisingBatchTransform, DenoisingPatchTransform, ImageFitter, SegmentationPatchTransform
 
 
 def kfold_indices(n: int, folds: int, seed: Optional[int] = None):
@@ -100,3 +105,63 @@ def run_denoising(noisy: np.ndarray, clean: np.ndarray, n_epochs: int = 5, folds
     # per-image scores of all folds (not the spread of the fold means)
     allv = np.concatenate([np.asarray(r, dtype=np.float64).reshape(-1) for r in results])
     return {"psnr": results, "psnr_mean": float(allv.mean()), "psnr_std": float(allv.std()), "history": histories}
+
+
+class VolumeLoader:
+    """`BatchLoader` for volumes whose sizes may differ: lists of (D,H,W) int16 volumes and uint8 label masks -> {'x','y'}
+    patch batches via a `SegmentationPatchTransform`, `per_step` volumes a batch.  Re-iterable (one pass per epoch)."""
+
+    def __init__(self, volumes, truths, idx: Sequence[int], per_step: int, transform, shuffle: bool, seed: int = 0):
+        self.volumes, self.truths, self.idx, self.bs, self.tf, self.shuffle = volumes, truths, np.asarray(idx), per_step, transform, shuffle
+        self.rs = np.random.RandomState(seed)
+
+    def __len__(self):
+        return (len(self.idx) + self.bs - 1) // self.bs
+
+    def __iter__(self):
+        order = self.rs.permutation(self.idx) if self.shuffle else self.idx
+        for i in range(0, len(order), self.bs):
+            sel = order[i:i + self.bs]
+            yield self.tf([self.volumes[k] for k in sel], [self.truths[k] for k in sel])
+
+
+def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_string: str = "lite", lr: float = 1e-4,
+                     batch_size: int = 8, im_size: int = 224, folder: str = "models", seed: int = 0, dtype=torch.bfloat16,
+                     callbacks: Optional[List[Callable[[int, Dict], None]]] = None, verbose: bool = False,
+                     crops_per_volume: int = 8, fg: float = 0.5, window=(-1024.0, 1024.0), label: int = -1, ls: float = 0.0,
+                     ensemble: int = 1, model_kwargs: Optional[Dict] = None) -> Dict:
+    """volumes / truths: sequences of (D,H,W) (or (H,W)) int16 volumes and uint8 label masks of the same shapes; sizes may
+    differ from volume to volume, every slice at least im_size x im_size.  K-fold over the volumes; per fold a 1-channel
+    preset model (`model_kwargs` overrides preset fields, e.g. patch_size) trains on `crops_per_volume` im_size patches per
+    volume, a share `fg` of them around foreground (`batch_size` counts patches: batch_size // crops_per_volume volumes per
+    step), validates on one centred crop per test volume and is scored by the hard Dice of its whole test volumes
+    (`functions.dice_tiled(window=, label=, ensemble=)`).
+    Returns {'dice': [per-fold arrays], 'dice_mean', 'dice_std', 'history'}, mean / std over all per-volume scores."""
+    assert len(volumes) == len(truths), f"{len(volumes)} volumes and {len(truths)} truths"
+    assert crops_per_volume >= 1 and batch_size % crops_per_volume == 0, \
+        f"batch_size {batch_size} (patches) must be a multiple of crops_per_volume {crops_per_volume}"
+    results, histories = [], []
+    for fold, (train_idx, test_idx) in enumerate(kfold_indices(len(volumes), folds, seed)):
+        if verbose:
+            print(f"FOLD {fold}: Training on {len(train_idx)} volumes and testing on {len(test_idx)} volumes")
+        train = VolumeLoader(volumes, truths, train_idx, batch_size // crops_per_volume,
+                             SegmentationPatchTransform(im_size, crops_per_volume, train=True, window=window, ls=ls, fg=fg, label=label,
+                                                        seed=seed + fold), shuffle=True, seed=seed + fold)
+        test = VolumeLoader(volumes, truths, test_idx, batch_size,
+                            SegmentationPatchTransform(im_size, train=False, window=window, ls=ls, label=label), shuffle=False)
+        model = models.get_vit_unet(model_string, dtype=dtype, **{**(model_kwargs or {}), "num_channels": 1, "im_size": im_size})
+        model.to("cuda")
+        optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
+        fitter = ImageFitter(model, loss=fn.DiceLoss(), optimizer=optimizer, device="cuda", folder=folder, seed=seed + fold)
+        cbs = [(lambda log, f=fold, cb=cb: cb(f, log)) for cb in (callbacks or [])]
+        histories.append(fitter.fit(train, test, n_epochs=n_epochs, callbacks=cbs, verbose=verbose))
+        fitter.load(os.path.join(folder, "best-checkpoint.bin"))
+        model = fitter.model
+        model.eval()
+        score = fn.dice_tiled(model, ((volumes[i], truths[i]) for i in test_idx), overlap=min(32, im_size // 2), window=window,
+                              label=label, ensemble=ensemble)
+        if verbose:
+            print(f"FOLD {fold}: Mean Dice {np.mean(score)}")
+        results.append(score)
+    allv = np.concatenate([np.asarray(r, dtype=np.float64).reshape(-1) for r in results])
+    return {"dice": results, "dice_mean": float(allv.mean()), "dice_std": float(allv.std()), "history": histories}
