@@ -376,6 +376,52 @@ int vu_segpatch_draw(const uint8_t* mask, const uint32_t* index, const uint32_t*
 int vu_patch_pairs_i16(const int16_t* vol, const uint8_t* mask, float* x, float* y, int D, int H, int W, int T, const int* crops, int n,
                        float lo, float hi, float ls, int label, void* stream);
 
+/* Segmentation mask clean-up: connected components on the device (csrc/vu_segclean.hip; no reference counterpart).  mask is
+ * (D,H,W) uint8 (one slice: D = 1), a pixel's linear index is i = (z H + y) W + x, D H W <= 2^31 - 1.
+ * Units and connectivity: conn 4 or 8 labels every slice on its own (U = D units; 4: edge neighbours, 8: edge and corner
+ * neighbours); conn 6 or 26 labels the volume as one unit (U = 1; 6: face neighbours, 26: face, edge and corner neighbours) and
+ * needs D >= 2 - a single slice has no 3-D connectivity and takes 4 or 8.
+ *   cc_tile      the tile height and width of the labelling kernel (16 x 64), so that a test can put structures on tile borders.
+ *   cc_label     fg = 1 labels the pixels with mask != 0, fg = 0 those with mask == 0 (the background, for hole filling).
+ *                  labels (D,H,W) int32: -1 on an unlabelled pixel, else the smallest linear index of the pixel's component
+ *                  sizes  (D,H,W) uint32, may be NULL: sizes[r] = pixels of the component whose smallest index is r, 0 elsewhere
+ *                scratch >= vu_cc_scratch_bytes(D, H, W), 4-byte aligned; after the call its first uint32 is the overflow word
+ *                (below; 0 on every input the bounds cover).  mask, labels, sizes and scratch must not overlap.
+ *   seg_clean    the steps, in this fixed order:
+ *                  1. label the foreground (mask != 0) with conn;
+ *                  2. drop the components with size < min_size;
+ *                  3. keep_largest: keep only the unit's largest remaining component, ties to the smallest root index; a unit with
+ *                     nothing left stays empty;
+ *                  4. fill_holes: label the background of that result with the dual connectivity (8 -> 4, 4 -> 8, 26 -> 6, 6 -> 26)
+ *                     and set to 1 every background component that touches no border of its unit: the four slice edges for a
+ *                     per-slice unit, the six volume faces for a volume unit.
+ *                out (D,H,W) uint8 holds 0 or 1; it may be `mask` itself (any other overlap is refused).
+ *                counts (D,3) uint64, ALWAYS per slice: mask pixels, truth pixels, common pixels of the cleaned mask, with the truth
+ *                  rule and `label` of the seg-blend call above (truth != 0 when label < 0, truth == label when 0 <= label <= 255)
+ *                  and its two-stage fixed-order sum.  counts and truth are given together or both NULL.
+ *                stats (U,4) int64, may be NULL: components found by step 1, components kept after step 3, size of the largest
+ *                  component step 1 found, overflow.
+ *                scratch >= vu_seg_clean_scratch_bytes(D, H, W), 16-byte aligned (labels, sizes, per-unit accumulators, partial counts).
+ * Overflow: every data-dependent loop of the labelling (find, union retry) has an iteration cap derived from a bound - the 1024
+ * pixels of a tile inside a tile, 1 + tiles of the unit x 512 local components across tiles; a loop that reaches its cap sets the
+ * overflow word and leaves, so a wrong bound shows as a non-zero word and a wrong label, never as a hang.
+ * Reproducibility: the labelling unites with integer atomicMin, sizes and border flags are integer atomicAdd / atomicOr (summed per
+ * tile and local component in LDS first: one global add per tile and local component), the selection is a 64-bit integer
+ * atomicMax.  Integer sums, minima, maxima and ors do not depend on the order of arrival, so labels, sizes, out, counts and stats
+ * are fully defined by the input: the same bits on every run, whatever the launch order.
+ * Refused before any launch (VU_EINVAL): conn outside {4, 8, 6, 26}; conn 6 or 26 with D = 1; D H W > 2^31 - 1 or an empty
+ * volume; fg outside {0, 1}; keep_largest or fill_holes outside {0, 1}; label > 255; null mask / labels / out / scratch; a short or
+ * misaligned scratch; truth without counts or counts without truth; overlapping buffers.  W % 4 == 0 and aligned buffers take
+ * 4-byte mask / out / truth and 16-byte label accesses, anything else scalar ones. */
+int vu_cc_tile(int* th, int* tw);
+size_t vu_cc_scratch_bytes(int D, int H, int W);
+int vu_cc_label(const uint8_t* mask, int32_t* labels, uint32_t* sizes, void* scratch, size_t scratch_bytes, int D, int H, int W,
+                int conn, int fg, void* stream);
+size_t vu_seg_clean_scratch_bytes(int D, int H, int W);
+int vu_seg_clean(const uint8_t* mask, const uint8_t* truth, uint8_t* out, unsigned long long* counts, long long* stats, void* scratch,
+                 size_t scratch_bytes, int D, int H, int W, int conn, unsigned min_size, int keep_largest, int fill_holes, int label,
+                 void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

@@ -122,6 +122,11 @@ SIGNATURES = {
     "vu_tile_gather_i16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _ll, _i, _f, _f, _vp]),
     "vu_seg_blend_scratch_bytes": (_sz, [_i, _i, _i]),
     "vu_seg_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "vu_cc_tile": (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vu_cc_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vu_cc_label": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "vu_seg_clean_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vu_seg_clean": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, C.c_uint, _i, _i, _i, _vp]),
     "vu_dihedral_inverse": (_i, [_i]),
     "vu_patch_pairs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _vp]),
     "vu_dihedral_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

@@ -98,20 +98,21 @@ def _tiled_overlap(model, pairs, key, **kw):
 
 
 def dice_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-               label: int = -1, ensemble: int = 1):
+               label: int = -1, ensemble: int = 1, clean=None):
     """Hard Dice at full resolution over (volume_i16, truth_u8) pairs of (H,W) slices or (D,H,W) volumes: every volume goes
     through sliding-window inference (segment.TiledSegmenter) instead of a resize to im_size; the mask is sigmoid(logit) >=
     `threshold`, a truth pixel is truth != 0 (`label` < 0) or truth == label.  Returns one value per pair, from the
-    integer counts of the whole volume (1.0 when mask and truth are both empty)."""
+    integer counts of the whole volume (1.0 when mask and truth are both empty).  `clean`: a segment.MaskCleaner applied to
+    the thresholded mask before it is counted."""
     return _tiled_overlap(model, pairs, "dice", overlap=overlap, batch=batch, window=window, threshold=threshold, label=label,
-                          ensemble=ensemble)
+                          ensemble=ensemble, clean=clean)
 
 
 def iou_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-              label: int = -1, ensemble: int = 1):
+              label: int = -1, ensemble: int = 1, clean=None):
     """Intersection over union at full resolution (see `dice_tiled`)."""
     return _tiled_overlap(model, pairs, "iou", overlap=overlap, batch=batch, window=window, threshold=threshold, label=label,
-                          ensemble=ensemble)
+                          ensemble=ensemble, clean=clean)
 
 
 class _Dice(torch.autograd.Function):

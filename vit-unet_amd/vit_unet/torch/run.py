@@ -129,13 +129,13 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
                      batch_size: int = 8, im_size: int = 224, folder: str = "models", seed: int = 0, dtype=torch.bfloat16,
                      callbacks: Optional[List[Callable[[int, Dict], None]]] = None, verbose: bool = False,
                      crops_per_volume: int = 8, fg: float = 0.5, window=(-1024.0, 1024.0), label: int = -1, ls: float = 0.0,
-                     ensemble: int = 1, model_kwargs: Optional[Dict] = None) -> Dict:
+                     ensemble: int = 1, model_kwargs: Optional[Dict] = None, clean=None) -> Dict:
     """volumes / truths: sequences of (D,H,W) (or (H,W)) int16 volumes and uint8 label masks of the same shapes; sizes may
     differ from volume to volume, every slice at least im_size x im_size.  K-fold over the volumes; per fold a 1-channel
     preset model (`model_kwargs` overrides preset fields, e.g. patch_size) trains on `crops_per_volume` im_size patches per
     volume, a share `fg` of them around foreground (`batch_size` counts patches: batch_size // crops_per_volume volumes per
     step), validates on one centred crop per test volume and is scored by the hard Dice of its whole test volumes
-    (`functions.dice_tiled(window=, label=, ensemble=)`).
+    (`functions.dice_tiled(window=, label=, ensemble=, clean=)`; `clean` is a segment.MaskCleaner or None).
     Returns {'dice': [per-fold arrays], 'dice_mean', 'dice_std', 'history'}, mean / std over all per-volume scores."""
     assert len(volumes) == len(truths), f"{len(volumes)} volumes and {len(truths)} truths"
     assert crops_per_volume >= 1 and batch_size % crops_per_volume == 0, \
@@ -159,7 +159,7 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
         model = fitter.model
         model.eval()
         score = fn.dice_tiled(model, ((volumes[i], truths[i]) for i in test_idx), overlap=min(32, im_size // 2), window=window,
-                              label=label, ensemble=ensemble)
+                              label=label, ensemble=ensemble, clean=clean)
         if verbose:
             print(f"FOLD {fold}: Mean Dice {np.mean(score)}")
         results.append(score)

@@ -8,6 +8,10 @@ volume - the integer overlap counts that Dice and IoU are made of.  Cutting (wit
 `SegmentationBatchTransform`), blending, thresholding and counting are the HIP kernels of csrc/vu_segtile.hip (C ABI
 `vu_tile_gather_i16`, `vu_seg_blend`; documented in include/vit_unet_amd.h); the model call in the middle is the
 unchanged `vu_model_forward` path.  No CPU fallback.
+
+`MaskCleaner` is the stage after the threshold: connected components on the device (csrc/vu_segclean.hip, C ABI
+`vu_cc_label`, `vu_seg_clean`) - drop small components, keep the largest, fill enclosed holes - on a mask that never leaves
+the GPU.  `TiledSegmenter(clean=MaskCleaner(...))` returns and scores the cleaned mask.
 """
 from __future__ import annotations
 
@@ -41,6 +45,115 @@ def logit_threshold(threshold: float) -> float:
     return float(np.float32(math.log(thr / (1.0 - thr))))
 
 
+class MaskCleaner:
+    """`c = MaskCleaner(connectivity=8, min_size=0, keep_largest=False, fill_holes=False); clean = c(mask)`.
+
+    mask (H,W) or (D,H,W) uint8 (numpy or torch, host or device; a list / tuple gives a list); any non-zero value is
+    foreground.  connectivity 4 / 8 labels every slice on its own, 6 / 26 the whole (D,H,W) volume (refused for a single
+    slice).  The steps and their order are those of `vu_seg_clean` (include/vit_unet_amd.h): label, drop components smaller
+    than `min_size`, keep the largest remaining one per unit (ties to the smallest index), fill the background components
+    that touch no border of their unit (labelled with the dual connectivity).
+      cleaner(mask)                 the cleaned {0,1} uint8 mask of the input's shape, on the device
+      cleaner.labels(mask)          (labels int32: -1 on background, else the smallest linear index of the component;
+                                    sizes int64: the component's pixel count at that index, 0 elsewhere), both of mask's shape
+      cleaner.score(mask, truth, label=-1)   {"mask", "counts" (D,3) int64 on the host, "dice", "iou", "stats" (U,4) int64 on the
+                                    host: components found, kept, largest size, overflow}; raises VuError on a non-zero overflow
+    No CPU fallback: the mask is moved to 'cuda'.  Argument errors raise `VuError` before any launch."""
+
+    def __init__(self, connectivity: int = 8, min_size: int = 0, keep_largest: bool = False, fill_holes: bool = False):
+        if connectivity not in (4, 8, 6, 26):
+            raise VuError(f"connectivity must be 4 or 8 (slice by slice), 6 or 26 (the volume) (got {connectivity!r})")
+        if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or not 0 <= int(min_size) <= 0xffffffff:
+            raise VuError(f"min_size must be an integer in 0 .. 2^32 - 1 (got {min_size!r})")
+        self.connectivity, self.min_size = int(connectivity), int(min_size)
+        self.keep_largest, self.fill_holes = bool(keep_largest), bool(fill_holes)
+
+    def _mask(self, mask, what="mask"):
+        m = TiledSegmenter._volume(mask, torch.uint8, what)
+        if self.connectivity in (6, 26) and (m.dim() == 2 or m.shape[0] == 1):
+            raise VuError(f"connectivity {self.connectivity} needs a (D,H,W) volume with D >= 2 (got {tuple(m.shape)}); a slice takes 4 or 8")
+        if m.numel() > 0x7fffffff:
+            raise VuError(f"{what} {tuple(m.shape)} exceeds 2^31 - 1 pixels")
+        return m
+
+    @staticmethod
+    def _to_device(t):
+        if not torch.cuda.is_available():
+            raise VuError("MaskCleaner runs on the MI355X only (no CPU fallback)")
+        return (t if t.is_cuda else t.to("cuda", non_blocking=True)).contiguous()
+
+    def __call__(self, mask):
+        if isinstance(mask, (list, tuple)):
+            return [self(m) for m in mask]
+        m = self._mask(mask)
+        shape = tuple(m.shape)
+        m = self._to_device(m).reshape((-1,) + shape[-2:])
+        with torch.cuda.device(m.device):
+            return self.run(m, None)["mask"].reshape(shape)
+
+    def labels(self, mask):
+        if isinstance(mask, (list, tuple)):
+            return [self.labels(m) for m in mask]
+        m = self._mask(mask)
+        shape = tuple(m.shape)
+        m = self._to_device(m).reshape((-1,) + shape[-2:])
+        L = lib()
+        D, H, W = (int(s) for s in m.shape)
+        with torch.cuda.device(m.device):
+            labels = torch.empty(D, H, W, dtype=torch.int32, device=m.device)
+            sizes = torch.empty(D, H, W, dtype=torch.int32, device=m.device)
+            nbytes = int(L.vu_cc_scratch_bytes(D, H, W))
+            scratch = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=m.device)
+            check(L.vu_cc_label(ptr(m), ptr(labels), ptr(sizes), ptr(scratch), nbytes, D, H, W, self.connectivity, 1,
+                                stream_ptr(m.device)), "vu_cc_label")
+            if int(scratch[0]) != 0:
+                raise VuError("vu_cc_label: an iteration cap was reached (overflow): the labels are not valid")
+        return labels.reshape(shape), sizes.reshape(shape).to(torch.int64)
+
+    def score(self, mask, truth, label: int = -1):
+        if int(label) > 255:
+            raise VuError(f"label must be negative (any non-zero truth) or 0 .. 255 (got {label})")
+        m, t = self._mask(mask), TiledSegmenter._volume(truth, torch.uint8, "truth")
+        if tuple(m.shape) != tuple(t.shape):
+            raise VuError(f"the truth {tuple(t.shape)} does not have the mask's shape {tuple(m.shape)}")
+        shape = tuple(m.shape)
+        m = self._to_device(m).reshape((-1,) + shape[-2:])
+        t = t.to(m.device, non_blocking=True).contiguous().reshape(m.shape)
+        with torch.cuda.device(m.device):
+            res = self.run(m, t, int(label))
+        return self.finish(res, shape)
+
+    @staticmethod
+    def finish(res, shape):
+        """Host side of a scored `run`: counts and stats to the host, the overflow check, Dice and IoU of the whole volume."""
+        counts, stats = res["counts"].cpu(), res["stats"].cpu()
+        if int(stats[:, 3].max()) != 0:
+            raise VuError("vu_seg_clean: an iteration cap was reached (overflow): the cleaned mask is not valid")
+        pred, true, both = (int(c) for c in counts.sum(0))
+        return {"mask": res["mask"].reshape(shape), "counts": counts, "dice": dice_from_counts(pred, true, both),
+                "iou": iou_from_counts(pred, true, both), "stats": stats}
+
+    def run(self, mask: torch.Tensor, truth, label: int = -1, out=None):
+        """One vu_seg_clean on a (D,H,W) uint8 device mask (and truth): {"mask", "stats" (U,4) int64 and, with a truth,
+        "counts" (D,3) int64}, all on the device.  `out` may be `mask` itself."""
+        L = lib()
+        D, H, W = (int(s) for s in mask.shape)
+        if self.connectivity in (6, 26) and D == 1:
+            raise VuError(f"connectivity {self.connectivity} needs a volume with D >= 2 (got one slice); a slice takes 4 or 8")
+        dev = mask.device
+        U = 1 if self.connectivity in (6, 26) else D
+        res = {"mask": torch.empty(D, H, W, dtype=torch.uint8, device=dev) if out is None else out,
+               "stats": torch.empty(U, 4, dtype=torch.int64, device=dev)}
+        if truth is not None:
+            res["counts"] = torch.empty(D, 3, dtype=torch.int64, device=dev)
+        nbytes = int(L.vu_seg_clean_scratch_bytes(D, H, W))
+        scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=dev)
+        check(L.vu_seg_clean(ptr(mask), ptr(truth), ptr(res["mask"]), ptr(res.get("counts")), ptr(res["stats"]), ptr(scratch),
+                             nbytes, D, H, W, self.connectivity, self.min_size, int(self.keep_largest), int(self.fill_holes),
+                             int(label), stream_ptr(dev)), "vu_seg_clean")
+        return res
+
+
 class TiledSegmenter:
     """`s = TiledSegmenter(model, overlap=32, batch=64); mask = s(vol)`.
 
@@ -59,10 +172,15 @@ class TiledSegmenter:
     group's output buffer; one vu_seg_blend per group.  `ensemble` in {1, 2, 4, 8} is `TiledRestorer`'s self-ensemble (the
     same op sets and vu_dihedral_f32 loop) on the logits; `ensemble=1` launches none of those kernels.  The model's mode,
     running statistics and counters are untouched.  Argument errors raise `VuError` before any launch; a model that is not on
-    'cuda' is refused at the call, as `TiledRestorer` does."""
+    'cuda' is refused at the call, as `TiledRestorer` does.
+
+    `clean`: a `MaskCleaner`.  After the last blend one `vu_seg_clean` runs on the whole thresholded volume, in place:
+    output="mask" is the cleaned mask, `score` gives counts, Dice and IoU of the cleaned mask plus "stats" (the cleaner's) and
+    "raw_counts" (those of the thresholded mask); "logits" / "prob" with a cleaner are refused.  `clean=None` launches nothing
+    new."""
 
     def __init__(self, model, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-                 label: int = -1, ensemble: int = 1):
+                 label: int = -1, ensemble: int = 1, clean=None):
         T = int(model.im_size)
         if int(model.num_channels) != 1:
             raise VuError(f"a segmentation model has 1 channel (this one has {model.num_channels})")
@@ -77,6 +195,9 @@ class TiledSegmenter:
             raise VuError(f"label must be negative (any non-zero truth) or 0 .. 255 (got {label})")
         if ensemble not in TiledRestorer.ENSEMBLE_OPS:
             raise VuError(f"ensemble must be one of {sorted(TiledRestorer.ENSEMBLE_OPS)} (got {ensemble!r})")
+        if clean is not None and not isinstance(clean, MaskCleaner):
+            raise VuError(f"clean must be a MaskCleaner or None (got {type(clean).__name__})")
+        self.clean = clean
         self.zthr = logit_threshold(threshold)
         self.model, self.T, self.overlap, self.batch = model, T, int(overlap), int(batch)
         self.window, self.threshold, self.label, self.ensemble = (lo, hi), float(threshold), int(label), int(ensemble)
@@ -102,13 +223,19 @@ class TiledSegmenter:
             return [self(v, output) for v in vol]
         if output not in ("mask", "logits", "prob"):
             raise VuError(f"output must be 'mask', 'logits' or 'prob' (got {output!r})")
+        if self.clean is not None and output != "mask":
+            raise VuError(f"a cleaner works on the mask: output={output!r} with clean= is refused")
         v = self._volume(vol, torch.int16, "volume")
+        self._check_clean(v)
         dev = self._device()
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
         with torch.no_grad():
             if output == "mask":
-                return self._run(v, None, mask=True)["mask"].reshape(shape)
+                m = self._run(v, None, mask=True)["mask"]
+                if self.clean is not None:
+                    m = self.clean.run(m, None, out=m)["mask"]
+                return m.reshape(shape)
             z = self._run(v, None, logits=True)["logits"].reshape(shape)
             return z if output == "logits" else torch.sigmoid(z)
 
@@ -116,16 +243,27 @@ class TiledSegmenter:
         v, t = self._volume(vol, torch.int16, "volume"), self._volume(truth, torch.uint8, "truth")
         if tuple(v.shape) != tuple(t.shape):
             raise VuError(f"the truth {tuple(t.shape)} does not have the volume's shape {tuple(v.shape)}")
+        self._check_clean(v)
         dev = self._device()
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
         t = t.to(dev, non_blocking=True).contiguous().reshape(v.shape)
         with torch.no_grad():
             res = self._run(v, t, mask=True)
+            if self.clean is not None:
+                raw = res["counts"].cpu()
+                out = MaskCleaner.finish(self.clean.run(res["mask"], t, self.label, out=res["mask"]), shape)
+                out["raw_counts"] = raw
+                return out
         counts = res["counts"].cpu()
         pred, true, both = (int(c) for c in counts.sum(0))
         return {"mask": res["mask"].reshape(shape), "counts": counts, "dice": dice_from_counts(pred, true, both),
                 "iou": iou_from_counts(pred, true, both)}
+
+    def _check_clean(self, v):
+        c = self.clean
+        if c is not None and c.connectivity in (6, 26) and (v.dim() == 2 or v.shape[0] == 1):
+            raise VuError(f"connectivity {c.connectivity} needs a (D,H,W) volume with D >= 2 (got {tuple(v.shape)}); a slice takes 4 or 8")
 
     def _run(self, vol: torch.Tensor, truth, logits: bool = False, mask: bool = False):
         L, T, ov, m = lib(), self.T, self.overlap, self.model
