@@ -422,6 +422,55 @@ int vu_seg_clean(const uint8_t* mask, const uint8_t* truth, uint8_t* out, unsign
                  size_t scratch_bytes, int D, int H, int W, int conn, unsigned min_size, int keep_largest, int fill_holes, int label,
                  void* stream);
 
+/* Surface-distance metrics for segmentation (csrc/vu_segdist.hip; no reference counterpart): an exact Euclidean distance transform,
+ * the surface of a mask, and the integers the Hausdorff distance, its percentiles, the average symmetric surface distance and the
+ * surface Dice are made of.  mask is (D,H,W) uint8, D H W <= 2^31 - 1.
+ * Units: dims 2 treats every slice as a unit (U = D), dims 3 the volume as one unit (U = 1; refused for D = 1, as conn 6 / 26 above).
+ * Spacing: three positive integers (sz, sy, sx) in a unit the caller chooses (tenths of a millimetre, say).  The squared distance
+ * between two pixels is (sz dz)^2 + (sy dy)^2 + (sx dx)^2, an integer; dz = 0 for dims 2.  A call is refused when
+ * (sz (D-1))^2 + (sy (H-1))^2 + (sx (W-1))^2 > 2^31 - 1 (without the sz term for dims 2): every intermediate then fits in 32 bits and
+ * 0xffffffff is free to mean "no site".  The truth rule and `label` are those of the seg-blend call above (truth != 0 when label < 0,
+ * truth == label when 0 <= label <= 255); a prediction pixel is mask != 0.
+ *   edt_sq        fg = 1: the sites are the pixels with mask != 0; fg = 0: those with mask == 0.
+ *                   dist2 (D,H,W) uint32 = the minimum squared distance to a site of the same unit: 0 on a site, 0xffffffff
+ *                   everywhere in a unit without a site.  The exact minimum (a separable lower-envelope transform, no chamfer or
+ *                   jump-flooding approximation).  scratch >= vu_edt_scratch_bytes(D, H, W, dims), 4-byte aligned.
+ *   mask_surface  surf (D,H,W) uint8 = 1 on a foreground pixel with at least one of its 4 (dims 2) or 6 (dims 3) axis neighbours in the
+ *                   background or outside the unit, else 0 - a foreground pixel on the edge of its unit is surface: the rule
+ *                   input ^ binary_erosion(input) of MedPy / SciPy.  Foreground: mask != 0 when label < 0, mask == label otherwise.
+ *   surface_dist  P = the surface of pred != 0, T = the surface of the truth under `label`; d(P->T) = the multiset of dist2-to-T over
+ *                 the pixels of P, d(T->P) its mirror.  Per unit u:
+ *                   stats (U,6) uint64: |P|, |T|, max d(P->T), max d(T->P), elements <= tol2 of d(P->T), of d(T->P)
+ *                   sums  (U,2) float64: the sum of sqrt((double) d2) over d(P->T), over d(T->P): per-block partials in a fixed
+ *                     geometry (1024 pixels a block), added per unit in a fixed order by a second launch; no floating-point atomics
+ *                   order (U,3,2) uint32: order statistics of set 0 = d(P->T), 1 = d(T->P), 2 = their union as multisets.  With n the
+ *                     set's size, lo = (qnum (n-1)) / qden in 64-bit integer division and hi = min(lo + 1, n - 1):
+ *                     order[u,s,0] = the lo-th smallest element counted from 0, order[u,s,1] = the hi-th - the two neighbours
+ *                     numpy.percentile(..., method="linear") interpolates between for q = 100 qnum / qden.  Found by radix select
+ *                     (integer histograms, 8 bits a pass) over the device-resident distances.  0 <= qnum <= qden <= 1000000.
+ *                   dist_pt, dist_tp (D,H,W) uint32, each may be NULL: the two distance maps, to T and to P.
+ *                 A unit in which P or T is empty: stats[0..1] are the counts, the maximum of the non-empty direction is 0xffffffff and
+ *                 that of the empty one 0, both "within" counts are 0, sums are 0 and all order entries 0xffffffff.
+ *                 pred may be `truth` itself.  scratch >= vu_surface_dist_scratch_bytes(D, H, W, dims), 16-byte aligned (two surfaces,
+ *                 two maps, the transform's scratch, per-block partials, selection state and histograms).
+ *   segdist_geometry  the lengths the kernels treat specially, so that a test can put sites on either side of each: line_piece = the
+ *                 piece of a y / z line one workgroup holds in LDS (128; a longer line is covered piece by piece), lines_per_group = the
+ *                 neighbouring lines one workgroup owns (64), row_chunk = the pixels of a row one wave scans per trip (256).
+ * Reproducibility: integer minima, maxima, sums and histogram counts plus the fixed-order float64 sum: the same bits on every run.
+ * Refused before any launch (VU_EINVAL): dims outside {2, 3}; dims 3 with D = 1; fg outside {0, 1}; a spacing < 1 or the bound above
+ * exceeded; D H W > 2^31 - 1 or an empty volume; label > 255; qden < 1 or > 1000000, qnum > qden; null mask / dist2 / surf / pred /
+ * truth / stats / sums / order / scratch; a short or misaligned scratch; overlapping buffers.  No size is refused because a line does
+ * not fit in LDS.  W % 4 == 0 and aligned buffers take 4-byte mask loads and 16-byte distance accesses in the row pass. */
+int vu_segdist_geometry(int* line_piece, int* lines_per_group, int* row_chunk);
+size_t vu_edt_scratch_bytes(int D, int H, int W, int dims);
+int vu_edt_sq(const uint8_t* mask, uint32_t* dist2, void* scratch, size_t scratch_bytes, int D, int H, int W, int dims, int fg, int sz,
+              int sy, int sx, void* stream);
+int vu_mask_surface(const uint8_t* mask, uint8_t* surf, int D, int H, int W, int dims, int label, void* stream);
+size_t vu_surface_dist_scratch_bytes(int D, int H, int W, int dims);
+int vu_surface_dist(const uint8_t* pred, const uint8_t* truth, unsigned long long* stats, double* sums, uint32_t* order,
+                    uint32_t* dist_pt, uint32_t* dist_tp, void* scratch, size_t scratch_bytes, int D, int H, int W, int dims, int sz,
+                    int sy, int sx, int label, uint32_t tol2, uint32_t qnum, uint32_t qden, void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

@@ -127,6 +127,13 @@ SIGNATURES = {
     "vu_cc_label": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "vu_seg_clean_scratch_bytes": (_sz, [_i, _i, _i]),
     "vu_seg_clean": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, C.c_uint, _i, _i, _i, _vp]),
+    "vu_segdist_geometry": (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vu_edt_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "vu_edt_sq": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "vu_mask_surface": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vu_surface_dist_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "vu_surface_dist": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint32, C.c_uint32,
+                             C.c_uint32, _vp]),
     "vu_dihedral_inverse": (_i, [_i]),
     "vu_patch_pairs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _vp]),
     "vu_dihedral_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

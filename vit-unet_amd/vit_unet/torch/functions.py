@@ -115,6 +115,39 @@ def iou_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0,
                           ensemble=ensemble, clean=clean)
 
 
+def _tiled_surface(model, pairs, key, surface, **kw):
+    from ._lib import VuError
+    from .segment import SurfaceDistance, TiledSegmenter
+    if not isinstance(surface, SurfaceDistance):
+        raise VuError(f"surface must be a segment.SurfaceDistance (got {type(surface).__name__})")
+    s = TiledSegmenter(model, surface=surface, **kw)
+    return np.array([s.score(vol, truth)["surface"][key] for vol, truth in pairs], dtype=np.float64)
+
+
+def hd95_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
+               label: int = -1, ensemble: int = 1, surface=None, clean=None):
+    """Percentile Hausdorff distance (the percentile of `surface`, 95 by default) at full resolution over (volume_i16,
+    truth_u8) pairs, beside `dice_tiled`: the mask of sliding-window inference, after `clean` if given, against the truth
+    under `label`, measured by `surface` (a segment.SurfaceDistance: units, spacing, tolerance, percentile; required).
+    One value per pair, in the spacing's unit: the pooled-set definition ("hd95" of segment.surface_metrics)."""
+    return _tiled_surface(model, pairs, "hd95", surface, overlap=overlap, batch=batch, window=window, threshold=threshold,
+                          label=label, ensemble=ensemble, clean=clean)
+
+
+def assd_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
+               label: int = -1, ensemble: int = 1, surface=None, clean=None):
+    """Average symmetric surface distance at full resolution (see `hd95_tiled`)."""
+    return _tiled_surface(model, pairs, "assd", surface, overlap=overlap, batch=batch, window=window, threshold=threshold,
+                          label=label, ensemble=ensemble, clean=clean)
+
+
+def nsd_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
+              label: int = -1, ensemble: int = 1, surface=None, clean=None):
+    """Surface Dice at the tolerance of `surface`, at full resolution (see `hd95_tiled`)."""
+    return _tiled_surface(model, pairs, "nsd", surface, overlap=overlap, batch=batch, window=window, threshold=threshold,
+                          label=label, ensemble=ensemble, clean=clean)
+
+
 class _Dice(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target, apply_sigmoid):

@@ -706,7 +706,7 @@ class HViT_UNet(nn.Module):
     def segment(self, vol, output: str = "mask", **kw):
         """Label mask of a whole int16 slice (H,W) or volume (D,H,W) of any size by sliding-window inference
         (segment.TiledSegmenter, built once per set of its keyword arguments - overlap, batch, window, threshold, label,
-        ensemble, clean - and kept).  `forward` is unchanged: it still resizes inputs of another size."""
+        ensemble, clean, surface - and kept).  `forward` is unchanged: it still resizes inputs of another size."""
         from .segment import TiledSegmenter
         key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items()))
         cache = self.__dict__.setdefault("_segmenters", {})

@@ -129,18 +129,21 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
                      batch_size: int = 8, im_size: int = 224, folder: str = "models", seed: int = 0, dtype=torch.bfloat16,
                      callbacks: Optional[List[Callable[[int, Dict], None]]] = None, verbose: bool = False,
                      crops_per_volume: int = 8, fg: float = 0.5, window=(-1024.0, 1024.0), label: int = -1, ls: float = 0.0,
-                     ensemble: int = 1, model_kwargs: Optional[Dict] = None, clean=None) -> Dict:
+                     ensemble: int = 1, model_kwargs: Optional[Dict] = None, clean=None, surface=None) -> Dict:
     """volumes / truths: sequences of (D,H,W) (or (H,W)) int16 volumes and uint8 label masks of the same shapes; sizes may
     differ from volume to volume, every slice at least im_size x im_size.  K-fold over the volumes; per fold a 1-channel
     preset model (`model_kwargs` overrides preset fields, e.g. patch_size) trains on `crops_per_volume` im_size patches per
     volume, a share `fg` of them around foreground (`batch_size` counts patches: batch_size // crops_per_volume volumes per
     step), validates on one centred crop per test volume and is scored by the hard Dice of its whole test volumes
     (`functions.dice_tiled(window=, label=, ensemble=, clean=)`; `clean` is a segment.MaskCleaner or None).
-    Returns {'dice': [per-fold arrays], 'dice_mean', 'dice_std', 'history'}, mean / std over all per-volume scores."""
+    Returns {'dice': [per-fold arrays], 'dice_mean', 'dice_std', 'history'}, mean / std over all per-volume scores.
+    `surface`: a segment.SurfaceDistance; the same inference pass then also measures every test volume's boundary and the
+    result gains 'hd95', 'assd', 'nsd' (per-fold arrays) and their '_mean' / '_std'.  None (default) launches nothing new."""
     assert len(volumes) == len(truths), f"{len(volumes)} volumes and {len(truths)} truths"
     assert crops_per_volume >= 1 and batch_size % crops_per_volume == 0, \
         f"batch_size {batch_size} (patches) must be a multiple of crops_per_volume {crops_per_volume}"
     results, histories = [], []
+    surf = {"hd95": [], "assd": [], "nsd": []}
     for fold, (train_idx, test_idx) in enumerate(kfold_indices(len(volumes), folds, seed)):
         if verbose:
             print(f"FOLD {fold}: Training on {len(train_idx)} volumes and testing on {len(test_idx)} volumes")
@@ -158,10 +161,25 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
         fitter.load(os.path.join(folder, "best-checkpoint.bin"))
         model = fitter.model
         model.eval()
-        score = fn.dice_tiled(model, ((volumes[i], truths[i]) for i in test_idx), overlap=min(32, im_size // 2), window=window,
-                              label=label, ensemble=ensemble, clean=clean)
+        if surface is None:
+            score = fn.dice_tiled(model, ((volumes[i], truths[i]) for i in test_idx), overlap=min(32, im_size // 2), window=window,
+                                  label=label, ensemble=ensemble, clean=clean)
+        else:   # one inference pass per volume for Dice and the boundary metrics
+            from .segment import TiledSegmenter
+            seg = TiledSegmenter(model, overlap=min(32, im_size // 2), window=window, label=label, ensemble=ensemble, clean=clean,
+                                 surface=surface)
+            scored = [seg.score(volumes[i], truths[i]) for i in test_idx]
+            score = np.array([r["dice"] for r in scored], dtype=np.float64)
+            for k in surf:
+                surf[k].append(np.array([r["surface"][k] for r in scored], dtype=np.float64))
         if verbose:
             print(f"FOLD {fold}: Mean Dice {np.mean(score)}")
         results.append(score)
     allv = np.concatenate([np.asarray(r, dtype=np.float64).reshape(-1) for r in results])
-    return {"dice": results, "dice_mean": float(allv.mean()), "dice_std": float(allv.std()), "history": histories}
+    out = {"dice": results, "dice_mean": float(allv.mean()), "dice_std": float(allv.std()), "history": histories}
+    if surface is not None:
+        for k, v in surf.items():
+            a = np.concatenate(v)
+            with np.errstate(invalid="ignore"):   # an empty mask or truth gives inf: the mean is inf, the spread undefined
+                out.update({k: v, k + "_mean": float(a.mean()), k + "_std": float(a.std())})
+    return out

@@ -12,11 +12,17 @@ unchanged `vu_model_forward` path.  No CPU fallback.
 `MaskCleaner` is the stage after the threshold: connected components on the device (csrc/vu_segclean.hip, C ABI
 `vu_cc_label`, `vu_seg_clean`) - drop small components, keep the largest, fill enclosed holes - on a mask that never leaves
 the GPU.  `TiledSegmenter(clean=MaskCleaner(...))` returns and scores the cleaned mask.
+
+`SurfaceDistance` adds the boundary metrics organ segmentation is reported with - Hausdorff distance, HD95, average symmetric
+surface distance, surface Dice - from an exact integer Euclidean distance transform on the device (csrc/vu_segdist.hip, C ABI
+`vu_edt_sq`, `vu_mask_surface`, `vu_surface_dist`); `TiledSegmenter(surface=SurfaceDistance(...))` scores the final mask with
+them.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -154,6 +160,200 @@ class MaskCleaner:
         return res
 
 
+NO_SITE = 0xffffffff   # vu_edt_sq / vu_surface_dist: no site in this unit
+
+
+def surface_metrics(stats, sums, order, qnum: int, qden: int) -> dict:
+    """The float64 part of the surface metrics, on the host, from the per-unit integers of `vu_surface_dist`
+    (include/vit_unet_amd.h): stats (U,6), sums (U,2), order (U,3,2), and the quantile qnum / qden they were selected for.
+    Per unit, with P and T the two surfaces:
+      hd             sqrt(max(max d(P->T), max d(T->P)))
+      hd95           sqrt(a) + (sqrt(b) - sqrt(a)) frac over the pooled set (order[u,2] = (a, b)), n = |P| + |T|,
+                     frac = (qnum (n - 1) mod qden) / qden: numpy.percentile(..., method="linear"), MedPy's definition
+      hd95_directed  the larger of the same interpolation over d(P->T) and over d(T->P): MONAI's definition
+      assd           (sum P->T + sum T->P) / (|P| + |T|)
+      nsd            (within P->T + within T->P) / (|P| + |T|)
+    A unit with both surfaces empty gives 0, 0, 0, 0 and nsd 1; one with exactly one surface empty inf, inf, inf, inf and nsd 0.
+    Returns the per-unit float64 arrays "hd_units", "hd95_units", "hd95_directed_units", "assd_units", "nsd_units", "units" =
+    the number of units that are not both-empty, and "hd", "hd95", "hd95_directed", "assd", "nsd" = the means over those
+    units (the values of a both-empty unit when there is no other)."""
+    st = np.asarray(stats).astype(np.int64).reshape(-1, 6)
+    sm = np.asarray(sums, dtype=np.float64).reshape(-1, 2)
+    od = np.asarray(order).astype(np.int64).reshape(-1, 3, 2)
+    qnum, qden = int(qnum), int(qden)
+    if not (1 <= qden and 0 <= qnum <= qden):
+        raise VuError(f"the quantile needs 0 <= qnum <= qden, qden >= 1 (got {qnum} / {qden})")
+    U = st.shape[0]
+    if sm.shape[0] != U or od.shape[0] != U:
+        raise VuError(f"stats, sums and order disagree on the number of units ({U}, {sm.shape[0]}, {od.shape[0]})")
+    names = ("hd", "hd95", "hd95_directed", "assd", "nsd")
+    per = {k: np.zeros(U, dtype=np.float64) for k in names}
+
+    def interp(pair, n):
+        a, b = math.sqrt(int(pair[0])), math.sqrt(int(pair[1]))
+        frac = ((qnum * (n - 1)) % qden) / qden
+        return a + (b - a) * frac
+
+    live = np.zeros(U, dtype=bool)
+    for u in range(U):
+        n_p, n_t = int(st[u, 0]), int(st[u, 1])
+        if n_p == 0 and n_t == 0:
+            per["nsd"][u] = 1.0
+            continue
+        live[u] = True
+        if n_p == 0 or n_t == 0:
+            for k in names[:4]:
+                per[k][u] = math.inf
+            continue
+        n = n_p + n_t
+        per["hd"][u] = math.sqrt(max(int(st[u, 2]), int(st[u, 3])))
+        per["hd95"][u] = interp(od[u, 2], n)
+        per["hd95_directed"][u] = max(interp(od[u, 0], n_p), interp(od[u, 1], n_t))
+        per["assd"][u] = (float(sm[u, 0]) + float(sm[u, 1])) / n
+        per["nsd"][u] = (int(st[u, 4]) + int(st[u, 5])) / n
+    out = {k + "_units": v for k, v in per.items()}
+    out["units"] = int(live.sum())
+    for k in names:
+        out[k] = float(per[k][live].mean()) if live.any() else (1.0 if k == "nsd" else 0.0)
+    return out
+
+
+class SurfaceDistance:
+    """`sd = SurfaceDistance(dims=2, spacing=(1, 1, 1), tolerance=1.0, percentile=95.0); res = sd.score(mask, truth)`.
+
+    Boundary metrics of a mask against a truth, from the exact squared Euclidean distance transform of `vu_edt_sq` on the
+    device.  dims 2 treats every slice as a unit, dims 3 the whole (D,H,W) volume (refused for a single slice).  `spacing` =
+    (sz, sy, sx): positive integers in a unit of the caller's choice (tenths of a millimetre, say); distances come out in that
+    unit, `tolerance` (of the surface Dice) is given in it and enters as tol2 = floor(tolerance^2) - exact, because squared
+    distances are integers.  `percentile` becomes qnum / qden = Fraction(percentile / 100).limit_denominator(10000).
+    Inputs as `MaskCleaner`: (H,W) or (D,H,W) uint8, numpy or torch, host or device; lists give lists.
+      sd.edt(mask, fg=True)            int64 of mask's shape: squared distance to the nearest pixel with mask != 0 (fg) or
+                                       mask == 0 (not fg) of the same unit, -1 where the unit has none
+      sd.surface(mask, label=-1)       uint8: the foreground pixels with an axis neighbour in the background or outside the unit
+      sd.score(mask, truth, label=-1)  {"stats" (U,6) int64, "sums" (U,2) float64, "order" (U,3,2) int64 on the host, as
+                                       `vu_surface_dist` defines them} plus everything `surface_metrics` returns: "hd", "hd95",
+                                       "hd95_directed", "assd", "nsd", their "*_units" arrays and "units"
+    No CPU fallback: the mask is moved to 'cuda'.  Argument errors raise `VuError` before any launch."""
+
+    def __init__(self, dims: int = 2, spacing=(1, 1, 1), tolerance: float = 1.0, percentile: float = 95.0):
+        if isinstance(dims, bool) or dims not in (2, 3):
+            raise VuError(f"dims must be 2 (slice by slice) or 3 (the volume) (got {dims!r})")
+        try:
+            sp = tuple(spacing)
+        except TypeError:
+            sp = ()
+        if len(sp) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 0x7fffffff for v in sp):
+            raise VuError(f"spacing must be three positive integers (sz, sy, sx) (got {spacing!r})")
+        if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)) \
+                or not math.isfinite(float(tolerance)) or float(tolerance) < 0.0:
+            raise VuError(f"tolerance must be a finite number >= 0 (got {tolerance!r})")
+        if isinstance(percentile, bool) or not isinstance(percentile, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(percentile) <= 100.0:
+            raise VuError(f"percentile must be a number in 0 .. 100 (got {percentile!r})")
+        self.dims, self.spacing = int(dims), tuple(int(v) for v in sp)
+        self.tolerance, self.percentile = float(tolerance), float(percentile)
+        t = Fraction(self.tolerance)
+        self.tol2 = min(int(math.floor(t * t)), 0x7fffffff)   # no squared distance is larger
+        q = (Fraction(self.percentile) / 100).limit_denominator(10000)
+        self.qnum, self.qden = int(q.numerator), int(q.denominator)
+
+    def _mask(self, mask, what="mask"):
+        m = TiledSegmenter._volume(mask, torch.uint8, what)
+        self._check_shape(tuple(m.shape))
+        return m
+
+    def _check_shape(self, shape):
+        if self.dims == 3 and (len(shape) == 2 or shape[0] == 1):
+            raise VuError(f"dims 3 needs a (D,H,W) volume with D >= 2 (got {tuple(shape)}); a slice takes dims 2")
+        D, H, W = (1,) * (3 - len(shape)) + tuple(int(v) for v in shape)
+        if D * H * W > 0x7fffffff:
+            raise VuError(f"{tuple(shape)} exceeds 2^31 - 1 pixels")
+        sz, sy, sx = self.spacing
+        far = (sy * (H - 1)) ** 2 + (sx * (W - 1)) ** 2 + ((sz * (D - 1)) ** 2 if self.dims == 3 else 0)
+        if far > 0x7fffffff:
+            raise VuError(f"the largest squared distance of {tuple(shape)} at spacing {self.spacing} is {far} > 2^31 - 1: use a coarser unit")
+
+    @staticmethod
+    def _to_device(t):
+        if not torch.cuda.is_available():
+            raise VuError("SurfaceDistance runs on the MI355X only (no CPU fallback)")
+        return (t if t.is_cuda else t.to("cuda", non_blocking=True)).contiguous()
+
+    def edt(self, mask, fg: bool = True):
+        if isinstance(mask, (list, tuple)):
+            return [self.edt(m, fg) for m in mask]
+        m = self._mask(mask)
+        shape = tuple(m.shape)
+        m = self._to_device(m).reshape((-1,) + shape[-2:])
+        L = lib()
+        D, H, W = (int(v) for v in m.shape)
+        with torch.cuda.device(m.device):
+            d2 = torch.empty(D, H, W, dtype=torch.int32, device=m.device)
+            nbytes = int(L.vu_edt_scratch_bytes(D, H, W, self.dims))
+            scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=m.device)
+            check(L.vu_edt_sq(ptr(m), ptr(d2), ptr(scratch), nbytes, D, H, W, self.dims, int(bool(fg)), *self.spacing,
+                              stream_ptr(m.device)), "vu_edt_sq")
+        return d2.reshape(shape).to(torch.int64)   # 0xffffffff -> -1, every distance < 2^31 unchanged
+
+    def surface(self, mask, label: int = -1):
+        if isinstance(mask, (list, tuple)):
+            return [self.surface(m, label) for m in mask]
+        if int(label) > 255:
+            raise VuError(f"label must be negative (any non-zero pixel) or 0 .. 255 (got {label})")
+        m = self._mask(mask)
+        shape = tuple(m.shape)
+        m = self._to_device(m).reshape((-1,) + shape[-2:])
+        D, H, W = (int(v) for v in m.shape)
+        with torch.cuda.device(m.device):
+            surf = torch.empty(D, H, W, dtype=torch.uint8, device=m.device)
+            check(lib().vu_mask_surface(ptr(m), ptr(surf), D, H, W, self.dims, int(label), stream_ptr(m.device)), "vu_mask_surface")
+        return surf.reshape(shape)
+
+    def score(self, mask, truth, label: int = -1):
+        if isinstance(mask, (list, tuple)):
+            return [self.score(m, t, label) for m, t in zip(mask, truth)]
+        if int(label) > 255:
+            raise VuError(f"label must be negative (any non-zero truth) or 0 .. 255 (got {label})")
+        m, t = self._mask(mask), TiledSegmenter._volume(truth, torch.uint8, "truth")
+        if tuple(m.shape) != tuple(t.shape):
+            raise VuError(f"the truth {tuple(t.shape)} does not have the mask's shape {tuple(m.shape)}")
+        shape = tuple(m.shape)
+        m = self._to_device(m).reshape((-1,) + shape[-2:])
+        t = t.to(m.device, non_blocking=True).contiguous().reshape(m.shape)
+        with torch.cuda.device(m.device):
+            res = self.run(m, t, int(label))
+        return self.finish(res)
+
+    def finish(self, res) -> dict:
+        """Host side of a `run`: the integers to the host and the float64 metrics of `surface_metrics`."""
+        stats = res["stats"].cpu()
+        sums = res["sums"].cpu()
+        order = res["order"].cpu().to(torch.int64) & 0xffffffff
+        out = {"stats": stats, "sums": sums, "order": order}
+        out.update(surface_metrics(stats.numpy(), sums.numpy(), order.numpy(), self.qnum, self.qden))
+        return out
+
+    def run(self, mask: torch.Tensor, truth: torch.Tensor, label: int = -1, maps: bool = False):
+        """One vu_surface_dist on (D,H,W) uint8 device tensors: {"stats" (U,6) int64, "sums" (U,2) float64, "order" (U,3,2)
+        int32 holding the uint32 bits} on the device; with `maps` also "dist_pt" / "dist_tp" (D,H,W) int32 bits."""
+        L = lib()
+        D, H, W = (int(v) for v in mask.shape)
+        self._check_shape((D, H, W))
+        dev = mask.device
+        U = 1 if self.dims == 3 else D
+        res = {"stats": torch.empty(U, 6, dtype=torch.int64, device=dev), "sums": torch.empty(U, 2, dtype=torch.float64, device=dev),
+               "order": torch.empty(U, 3, 2, dtype=torch.int32, device=dev)}
+        if maps:
+            res["dist_pt"] = torch.empty(D, H, W, dtype=torch.int32, device=dev)
+            res["dist_tp"] = torch.empty(D, H, W, dtype=torch.int32, device=dev)
+        nbytes = int(L.vu_surface_dist_scratch_bytes(D, H, W, self.dims))
+        scratch = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.int32, device=dev)
+        check(L.vu_surface_dist(ptr(mask), ptr(truth), ptr(res["stats"]), ptr(res["sums"]), ptr(res["order"]), ptr(res.get("dist_pt")),
+                                ptr(res.get("dist_tp")), ptr(scratch), nbytes, D, H, W, self.dims, *self.spacing, int(label),
+                                self.tol2, self.qnum, self.qden, stream_ptr(dev)), "vu_surface_dist")
+        return res
+
+
 class TiledSegmenter:
     """`s = TiledSegmenter(model, overlap=32, batch=64); mask = s(vol)`.
 
@@ -177,10 +377,14 @@ class TiledSegmenter:
     `clean`: a `MaskCleaner`.  After the last blend one `vu_seg_clean` runs on the whole thresholded volume, in place:
     output="mask" is the cleaned mask, `score` gives counts, Dice and IoU of the cleaned mask plus "stats" (the cleaner's) and
     "raw_counts" (those of the thresholded mask); "logits" / "prob" with a cleaner are refused.  `clean=None` launches nothing
-    new."""
+    new.
+
+    `surface`: a `SurfaceDistance`.  `score` then runs one `vu_surface_dist` on the final mask (after `clean`, if given)
+    against the truth under `label` and adds "surface": the dict of `SurfaceDistance.score`.  `surface=None` launches nothing
+    new and returns exactly the dicts above."""
 
     def __init__(self, model, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-                 label: int = -1, ensemble: int = 1, clean=None):
+                 label: int = -1, ensemble: int = 1, clean=None, surface=None):
         T = int(model.im_size)
         if int(model.num_channels) != 1:
             raise VuError(f"a segmentation model has 1 channel (this one has {model.num_channels})")
@@ -197,7 +401,9 @@ class TiledSegmenter:
             raise VuError(f"ensemble must be one of {sorted(TiledRestorer.ENSEMBLE_OPS)} (got {ensemble!r})")
         if clean is not None and not isinstance(clean, MaskCleaner):
             raise VuError(f"clean must be a MaskCleaner or None (got {type(clean).__name__})")
-        self.clean = clean
+        if surface is not None and not isinstance(surface, SurfaceDistance):
+            raise VuError(f"surface must be a SurfaceDistance or None (got {type(surface).__name__})")
+        self.clean, self.surface = clean, surface
         self.zthr = logit_threshold(threshold)
         self.model, self.T, self.overlap, self.batch = model, T, int(overlap), int(batch)
         self.window, self.threshold, self.label, self.ensemble = (lo, hi), float(threshold), int(label), int(ensemble)
@@ -244,6 +450,8 @@ class TiledSegmenter:
         if tuple(v.shape) != tuple(t.shape):
             raise VuError(f"the truth {tuple(t.shape)} does not have the volume's shape {tuple(v.shape)}")
         self._check_clean(v)
+        if self.surface is not None:
+            self.surface._check_shape(tuple(v.shape))
         dev = self._device()
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
@@ -254,11 +462,14 @@ class TiledSegmenter:
                 raw = res["counts"].cpu()
                 out = MaskCleaner.finish(self.clean.run(res["mask"], t, self.label, out=res["mask"]), shape)
                 out["raw_counts"] = raw
-                return out
-        counts = res["counts"].cpu()
-        pred, true, both = (int(c) for c in counts.sum(0))
-        return {"mask": res["mask"].reshape(shape), "counts": counts, "dice": dice_from_counts(pred, true, both),
-                "iou": iou_from_counts(pred, true, both)}
+            else:
+                counts = res["counts"].cpu()
+                pred, true, both = (int(c) for c in counts.sum(0))
+                out = {"mask": res["mask"].reshape(shape), "counts": counts, "dice": dice_from_counts(pred, true, both),
+                       "iou": iou_from_counts(pred, true, both)}
+            if self.surface is not None:
+                out["surface"] = self.surface.finish(self.surface.run(res["mask"], t, self.label))
+        return out
 
     def _check_clean(self, v):
         c = self.clean
