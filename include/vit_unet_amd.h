@@ -471,6 +471,43 @@ int vu_surface_dist(const uint8_t* pred, const uint8_t* truth, unsigned long lon
                     uint32_t* dist_pt, uint32_t* dist_tp, void* scratch, size_t scratch_bytes, int D, int H, int W, int dims, int sz,
                     int sy, int sx, int label, uint32_t tol2, uint32_t qnum, uint32_t qden, void* stream);
 
+/* ---- Volume resampling to a working spacing and back (csrc/vu_resample.hip; Python: segment.VolumeResampler) ----
+ * A (Di,Hi,Wi) volume becomes (Do,Ho,Wo).  Resampling is driven by the two shapes alone: an axis of n_in samples becomes n_out
+ * samples with half-pixel centres, output i sits at ((2 i + 1) n_in - n_out) / (2 n_out) of the input, edges replicated.  A spacing
+ * exists only in Python, where it chooses n_out.  All table arithmetic is exact integer, Q = 2^15 ("//" and "%" floor, on
+ * non-negative operands only):
+ *   linear table of an axis, (i0[i], w[i]):  num = (2 i + 1) n_in - n_out, den = 2 n_out.  num <= 0 gives (0, 0).  Otherwise
+ *       i0 = num // den, r = num % den, w = (2 Q r + den) // (2 den); i0 >= n_in - 1 gives (n_in - 1, 0).  The second tap is
+ *       i1 = min(i0 + 1, n_in - 1); 0 <= w <= Q; n_out == n_in gives the identity (i, 0).
+ *   nearest table, src[i] = ((2 i + 1) n_in) // (2 n_out), always in 0 .. n_in - 1.
+ *   resample_i16         trilinear, staged x, then y, then z.  A stage is (v0 (Q - w) + v1 w + Q / 2) >> 15 with an arithmetic shift
+ *                        (round half up); its result is again an int16 value and enters the next stage; |v| <= 2^15 keeps every
+ *                        intermediate inside int32.  The kernel does the 4 x-stages, 2 y-stages and 1 z-stage of an output in
+ *                        registers: the same bits as three passes.
+ *   resample_f32         the same tables and order on float32 (logits): wf = (float) w / Q (exact), a stage is a + (b - a) * wf with the
+ *                        subtraction, the product and the sum each rounded to float32 on its own (no fused multiply-add), also where
+ *                        w = 0.  out (Do,Ho,Wo) float32; mask uint8 = value >= zthr ? 1 : 0; counts (Do,3) uint64 per output slice:
+ *                        mask pixels, truth pixels, pixels where both are set, truth (Do,Ho,Wo) uint8 under the label rule of
+ *                        vu_seg_blend (truth != 0 when label < 0, truth == label when 0 .. 255).  out, mask and counts may each be
+ *                        NULL, not all three; counts need truth and scratch >= vu_resample_f32_scratch_bytes(Do, Ho, Wo), 4-byte
+ *                        aligned: per-workgroup partial counts, summed per slice in a fixed order by a second launch (no atomics).
+ *   resample_u8_nearest  out[z,y,x] = in[src_z[z], src_y[y], src_x[x]] for label masks of any values: no value is invented.
+ *   resample_axis_linear / _nearest   the tables themselves, host code without a GPU call; `capacity` >= n_out entries; return n_out.
+ *   resample_geometry    the tile of outputs one workgroup owns (128 x 8 x 1), so that a test can put shapes on either side of it.
+ * Integer results are exact and every output is bit-identical from run to run.  Refused before any launch (VU_EINVAL): a null
+ * pointer; a dimension < 1; more than 2^31 - 1 elements on either side; an output that overlaps an input (or, in resample_f32,
+ * another output or the scratch); label > 255; a zthr that is not a number; a short or misaligned scratch; counts not 8-byte aligned.
+ * Wo % 4 == 0 with an aligned output takes 8-byte (int16), 16-byte (float32) and 4-byte (uint8) stores, anything else scalar ones.
+ * No anti-alias filter runs before a strong reduction (nnU-Net's resampling has none either). */
+int vu_resample_axis_linear(int n_in, int n_out, int* i0, int* w, int capacity);
+int vu_resample_axis_nearest(int n_in, int n_out, int* src, int capacity);
+int vu_resample_geometry(int* tile_x, int* tile_y, int* tile_z);
+int vu_resample_i16(const int16_t* in, int16_t* out, int Di, int Hi, int Wi, int Do, int Ho, int Wo, void* stream);
+int vu_resample_u8_nearest(const uint8_t* in, uint8_t* out, int Di, int Hi, int Wi, int Do, int Ho, int Wo, void* stream);
+size_t vu_resample_f32_scratch_bytes(int Do, int Ho, int Wo);
+int vu_resample_f32(const float* in, const uint8_t* truth, float* out, uint8_t* mask, unsigned long long* counts, void* scratch,
+                    size_t scratch_bytes, int Di, int Hi, int Wi, int Do, int Ho, int Wo, float zthr, int label, void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

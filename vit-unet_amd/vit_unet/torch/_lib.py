@@ -134,6 +134,13 @@ SIGNATURES = {
     "vu_surface_dist_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "vu_surface_dist": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint32, C.c_uint32,
                              C.c_uint32, _vp]),
+    "vu_resample_axis_linear": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i]),
+    "vu_resample_axis_nearest": (_i, [_i, _i, C.POINTER(C.c_int), _i]),
+    "vu_resample_geometry": (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vu_resample_i16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vu_resample_u8_nearest": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vu_resample_f32_scratch_bytes": (_sz, [_i, _i, _i]),
+    "vu_resample_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "vu_dihedral_inverse": (_i, [_i]),
     "vu_patch_pairs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _vp]),
     "vu_dihedral_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

@@ -91,28 +91,39 @@ def ssim_tiled(model, pairs, overlap: int = 32, batch: int = 64, ensemble: int =
     return _tiled_scores(model, pairs, overlap, batch, ssim_batch, ensemble)
 
 
+def _scored(s, pairs):
+    """`s.score` over (volume, truth) pairs; with a resampler every item is (volume, truth, spacing): the volume's own voxel size
+    rides along as the item's third entry."""
+    for vol, truth, *sp in pairs:
+        if len(sp) > 1:
+            raise ValueError(f"expected (volume, truth) or (volume, truth, spacing) items, got {2 + len(sp)} entries")
+        yield s.score(vol, truth, spacing=sp[0]) if sp else s.score(vol, truth)
+
+
 def _tiled_overlap(model, pairs, key, **kw):
     from .segment import TiledSegmenter
     s = TiledSegmenter(model, **kw)
-    return np.array([s.score(vol, truth)[key] for vol, truth in pairs], dtype=np.float64)
+    return np.array([r[key] for r in _scored(s, pairs)], dtype=np.float64)
 
 
 def dice_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-               label: int = -1, ensemble: int = 1, clean=None):
+               label: int = -1, ensemble: int = 1, clean=None, resample=None):
     """Hard Dice at full resolution over (volume_i16, truth_u8) pairs of (H,W) slices or (D,H,W) volumes: every volume goes
     through sliding-window inference (segment.TiledSegmenter) instead of a resize to im_size; the mask is sigmoid(logit) >=
     `threshold`, a truth pixel is truth != 0 (`label` < 0) or truth == label.  Returns one value per pair, from the
     integer counts of the whole volume (1.0 when mask and truth are both empty).  `clean`: a segment.MaskCleaner applied to
-    the thresholded mask before it is counted."""
+    the thresholded mask before it is counted.  `resample`: a segment.VolumeResampler (or its target spacing); the items are
+    then (volume, truth, spacing) triples, the model runs at the working spacing and the mask is counted on the volume's own
+    grid (see `TiledSegmenter`).  None launches nothing new."""
     return _tiled_overlap(model, pairs, "dice", overlap=overlap, batch=batch, window=window, threshold=threshold, label=label,
-                          ensemble=ensemble, clean=clean)
+                          ensemble=ensemble, clean=clean, resample=resample)
 
 
 def iou_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-              label: int = -1, ensemble: int = 1, clean=None):
+              label: int = -1, ensemble: int = 1, clean=None, resample=None):
     """Intersection over union at full resolution (see `dice_tiled`)."""
     return _tiled_overlap(model, pairs, "iou", overlap=overlap, batch=batch, window=window, threshold=threshold, label=label,
-                          ensemble=ensemble, clean=clean)
+                          ensemble=ensemble, clean=clean, resample=resample)
 
 
 def _tiled_surface(model, pairs, key, surface, **kw):
@@ -121,31 +132,32 @@ def _tiled_surface(model, pairs, key, surface, **kw):
     if not isinstance(surface, SurfaceDistance):
         raise VuError(f"surface must be a segment.SurfaceDistance (got {type(surface).__name__})")
     s = TiledSegmenter(model, surface=surface, **kw)
-    return np.array([s.score(vol, truth)["surface"][key] for vol, truth in pairs], dtype=np.float64)
+    return np.array([r["surface"][key] for r in _scored(s, pairs)], dtype=np.float64)
 
 
 def hd95_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-               label: int = -1, ensemble: int = 1, surface=None, clean=None):
+               label: int = -1, ensemble: int = 1, surface=None, clean=None, resample=None):
     """Percentile Hausdorff distance (the percentile of `surface`, 95 by default) at full resolution over (volume_i16,
     truth_u8) pairs, beside `dice_tiled`: the mask of sliding-window inference, after `clean` if given, against the truth
     under `label`, measured by `surface` (a segment.SurfaceDistance: units, spacing, tolerance, percentile; required).
-    One value per pair, in the spacing's unit: the pooled-set definition ("hd95" of segment.surface_metrics)."""
+    One value per pair, in the spacing's unit: the pooled-set definition ("hd95" of segment.surface_metrics).  `resample`: as
+    in `dice_tiled` (items are (volume, truth, spacing) triples; the boundary is measured on the volume's own grid)."""
     return _tiled_surface(model, pairs, "hd95", surface, overlap=overlap, batch=batch, window=window, threshold=threshold,
-                          label=label, ensemble=ensemble, clean=clean)
+                          label=label, ensemble=ensemble, clean=clean, resample=resample)
 
 
 def assd_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-               label: int = -1, ensemble: int = 1, surface=None, clean=None):
+               label: int = -1, ensemble: int = 1, surface=None, clean=None, resample=None):
     """Average symmetric surface distance at full resolution (see `hd95_tiled`)."""
     return _tiled_surface(model, pairs, "assd", surface, overlap=overlap, batch=batch, window=window, threshold=threshold,
-                          label=label, ensemble=ensemble, clean=clean)
+                          label=label, ensemble=ensemble, clean=clean, resample=resample)
 
 
 def nsd_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-              label: int = -1, ensemble: int = 1, surface=None, clean=None):
+              label: int = -1, ensemble: int = 1, surface=None, clean=None, resample=None):
     """Surface Dice at the tolerance of `surface`, at full resolution (see `hd95_tiled`)."""
     return _tiled_surface(model, pairs, "nsd", surface, overlap=overlap, batch=batch, window=window, threshold=threshold,
-                          label=label, ensemble=ensemble, clean=clean)
+                          label=label, ensemble=ensemble, clean=clean, resample=resample)
 
 
 class _Dice(torch.autograd.Function):

@@ -703,16 +703,18 @@ class HViT_UNet(nn.Module):
             cache[key] = TiledRestorer(self, overlap=overlap, batch=batch, ensemble=ensemble)
         return cache[key](image)
 
-    def segment(self, vol, output: str = "mask", **kw):
+    def segment(self, vol, output: str = "mask", spacing=None, **kw):
         """Label mask of a whole int16 slice (H,W) or volume (D,H,W) of any size by sliding-window inference
         (segment.TiledSegmenter, built once per set of its keyword arguments - overlap, batch, window, threshold, label,
-        ensemble, clean, surface - and kept).  `forward` is unchanged: it still resizes inputs of another size."""
+        ensemble, clean, surface, resample - and kept).  With `resample=` (a segment.VolumeResampler or its target spacing)
+        `spacing` is the volume's own voxel size and the model runs at the working spacing.  `forward` is unchanged: it still
+        resizes inputs of another size."""
         from .segment import TiledSegmenter
         key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items()))
         cache = self.__dict__.setdefault("_segmenters", {})
         if key not in cache:
             cache[key] = TiledSegmenter(self, **kw)
-        return cache[key](vol, output)
+        return cache[key](vol, output) if spacing is None else cache[key](vol, output, spacing=spacing)
 
 
 def ViT_UNet(depth, depth_te, size_bottleneck, preprocessing, num_patches, patch_size, num_channels=3,

@@ -129,7 +129,8 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
                      batch_size: int = 8, im_size: int = 224, folder: str = "models", seed: int = 0, dtype=torch.bfloat16,
                      callbacks: Optional[List[Callable[[int, Dict], None]]] = None, verbose: bool = False,
                      crops_per_volume: int = 8, fg: float = 0.5, window=(-1024.0, 1024.0), label: int = -1, ls: float = 0.0,
-                     ensemble: int = 1, model_kwargs: Optional[Dict] = None, clean=None, surface=None) -> Dict:
+                     ensemble: int = 1, model_kwargs: Optional[Dict] = None, clean=None, surface=None, spacings=None,
+                     resample=None) -> Dict:
     """volumes / truths: sequences of (D,H,W) (or (H,W)) int16 volumes and uint8 label masks of the same shapes; sizes may
     differ from volume to volume, every slice at least im_size x im_size.  K-fold over the volumes; per fold a 1-channel
     preset model (`model_kwargs` overrides preset fields, e.g. patch_size) trains on `crops_per_volume` im_size patches per
@@ -138,8 +139,21 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
     (`functions.dice_tiled(window=, label=, ensemble=, clean=)`; `clean` is a segment.MaskCleaner or None).
     Returns {'dice': [per-fold arrays], 'dice_mean', 'dice_std', 'history'}, mean / std over all per-volume scores.
     `surface`: a segment.SurfaceDistance; the same inference pass then also measures every test volume's boundary and the
-    result gains 'hd95', 'assd', 'nsd' (per-fold arrays) and their '_mean' / '_std'.  None (default) launches nothing new."""
+    result gains 'hd95', 'assd', 'nsd' (per-fold arrays) and their '_mean' / '_std'.  None (default) launches nothing new.
+    `spacings` (one (sz, sy, sx) voxel size per volume) and `resample` (a segment.VolumeResampler or its target spacing), given
+    together: every volume and its truth are resampled once on the device to the working spacing (trilinear / nearest) and the
+    training and validation patches are cut from those (every resampled slice at least im_size x im_size); the test volumes are
+    scored on their own grids by `TiledSegmenter(resample=)`.  Without them nothing changes."""
     assert len(volumes) == len(truths), f"{len(volumes)} volumes and {len(truths)} truths"
+    assert (spacings is None) == (resample is None), "spacings= and resample= go together"
+    work_volumes, work_truths = volumes, truths
+    if resample is not None:
+        from .segment import VolumeResampler
+        assert len(spacings) == len(volumes), f"{len(volumes)} volumes and {len(spacings)} spacings"
+        if not isinstance(resample, VolumeResampler):
+            resample = VolumeResampler(resample)
+        work_volumes = resample.image(list(volumes), [tuple(s) for s in spacings])
+        work_truths = resample.labels(list(truths), [tuple(s) for s in spacings])
     assert crops_per_volume >= 1 and batch_size % crops_per_volume == 0, \
         f"batch_size {batch_size} (patches) must be a multiple of crops_per_volume {crops_per_volume}"
     results, histories = [], []
@@ -147,10 +161,10 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
     for fold, (train_idx, test_idx) in enumerate(kfold_indices(len(volumes), folds, seed)):
         if verbose:
             print(f"FOLD {fold}: Training on {len(train_idx)} volumes and testing on {len(test_idx)} volumes")
-        train = VolumeLoader(volumes, truths, train_idx, batch_size // crops_per_volume,
+        train = VolumeLoader(work_volumes, work_truths, train_idx, batch_size // crops_per_volume,
                              SegmentationPatchTransform(im_size, crops_per_volume, train=True, window=window, ls=ls, fg=fg, label=label,
                                                         seed=seed + fold), shuffle=True, seed=seed + fold)
-        test = VolumeLoader(volumes, truths, test_idx, batch_size,
+        test = VolumeLoader(work_volumes, work_truths, test_idx, batch_size,
                             SegmentationPatchTransform(im_size, train=False, window=window, ls=ls, label=label), shuffle=False)
         model = models.get_vit_unet(model_string, dtype=dtype, **{**(model_kwargs or {}), "num_channels": 1, "im_size": im_size})
         model.to("cuda")
@@ -161,14 +175,18 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
         fitter.load(os.path.join(folder, "best-checkpoint.bin"))
         model = fitter.model
         model.eval()
-        if surface is None:
+        if surface is None and resample is None:
             score = fn.dice_tiled(model, ((volumes[i], truths[i]) for i in test_idx), overlap=min(32, im_size // 2), window=window,
                                   label=label, ensemble=ensemble, clean=clean)
+        elif surface is None:
+            score = fn.dice_tiled(model, ((volumes[i], truths[i], tuple(spacings[i])) for i in test_idx), overlap=min(32, im_size // 2),
+                                  window=window, label=label, ensemble=ensemble, clean=clean, resample=resample)
         else:   # one inference pass per volume for Dice and the boundary metrics
             from .segment import TiledSegmenter
             seg = TiledSegmenter(model, overlap=min(32, im_size // 2), window=window, label=label, ensemble=ensemble, clean=clean,
-                                 surface=surface)
-            scored = [seg.score(volumes[i], truths[i]) for i in test_idx]
+                                 surface=surface, resample=resample)
+            scored = [seg.score(volumes[i], truths[i], **({} if resample is None else {"spacing": tuple(spacings[i])}))
+                      for i in test_idx]
             score = np.array([r["dice"] for r in scored], dtype=np.float64)
             for k in surf:
                 surf[k].append(np.array([r["surface"][k] for r in scored], dtype=np.float64))

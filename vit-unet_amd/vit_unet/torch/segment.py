@@ -17,6 +17,11 @@ the GPU.  `TiledSegmenter(clean=MaskCleaner(...))` returns and scores the cleane
 surface distance, surface Dice - from an exact integer Euclidean distance transform on the device (csrc/vu_segdist.hip, C ABI
 `vu_edt_sq`, `vu_mask_surface`, `vu_surface_dist`); `TiledSegmenter(surface=SurfaceDistance(...))` scores the final mask with
 them.
+
+`VolumeResampler` is the step around all of it: volumes and label masks of any voxel size are brought to one working spacing
+before patches and windows, and logits are brought back to the volume's own grid before the threshold (csrc/vu_resample.hip,
+C ABI `vu_resample_i16`, `vu_resample_u8_nearest`, `vu_resample_f32`); `TiledSegmenter(resample=VolumeResampler(...))` does
+both around the model and thresholds, cleans, counts and measures on the native grid.
 """
 from __future__ import annotations
 
@@ -354,6 +359,163 @@ class SurfaceDistance:
         return res
 
 
+class VolumeResampler:
+    """`r = VolumeResampler(target_spacing=(None, 1.0, 1.0)); work = r.image(vol, spacing)`.
+
+    Brings volumes of any voxel size to one working spacing and results back, on the device (csrc/vu_resample.hip, C ABI
+    `vu_resample_i16`, `vu_resample_u8_nearest`, `vu_resample_f32`; arithmetic in include/vit_unet_amd.h).  `target_spacing` =
+    (sz, sy, sx) in the unit of the caller's spacings; an entry may be None: that axis keeps its length ((None, s, s) is the
+    natural choice for the 2-D model).  Every spacing becomes Fraction(x).limit_denominator(10000); a `spacing` argument is
+    (sz, sy, sx) of the input, or (sy, sx) for an (H,W) input.
+      r.out_shape(shape, spacing)   n_out = max(1, floor(n_in s_in / s_out + 1/2)) per axis, in exact rational arithmetic
+      r.image(vol_i16, spacing)     the int16 volume on the working grid (trilinear, exact integer arithmetic), on the device
+      r.labels(mask_u8, spacing)    the uint8 label mask on the working grid (nearest: no label value is invented)
+      r.logits_to(z_f32, shape, truth=None, zthr=0.0, label=-1)
+                                    float32 logits brought to `shape` (the native grid): {"logits", "mask" uint8 = logit >= zthr}
+                                    and, with a `truth` uint8 of `shape`, "counts" (D,3) int64 on the device: mask pixels, truth
+                                    pixels, both, per slice (`label` as in `TiledSegmenter`)
+    Inputs are (H,W) or (D,H,W), numpy or torch, host or device; a list / tuple of inputs gives a list (with one spacing / shape
+    for all, or a list of them).  No CPU fallback: inputs are moved to 'cuda'.  Argument errors raise `VuError` before any launch."""
+
+    def __init__(self, target_spacing=(None, 1.0, 1.0)):
+        try:
+            sp = tuple(target_spacing)
+        except TypeError:
+            sp = ()
+        if len(sp) != 3:
+            raise VuError(f"target_spacing must be (sz, sy, sx), entries a positive number or None (got {target_spacing!r})")
+        self.target = tuple(None if v is None else self._fraction(v, "target_spacing") for v in sp)
+
+    @staticmethod
+    def _fraction(v, what) -> Fraction:
+        if isinstance(v, bool) or not isinstance(v, (int, float, Fraction, np.integer, np.floating)) or not math.isfinite(float(v)) \
+                or float(v) <= 0.0:
+            raise VuError(f"{what}: a spacing must be a finite number > 0 (got {v!r})")
+        f = (Fraction(int(v)) if isinstance(v, np.integer) else Fraction(float(v)) if isinstance(v, np.floating) else Fraction(v))
+        f = f.limit_denominator(10000)
+        if f <= 0:
+            raise VuError(f"{what}: the spacing {v!r} is below 1 / 10000")
+        return f
+
+    def _spacing(self, spacing, ndim):
+        try:
+            sp = tuple(spacing)
+        except TypeError:
+            sp = ()
+        if len(sp) == 2 and ndim == 2:
+            sp = (1,) + sp
+        if len(sp) != 3:
+            raise VuError(f"spacing must be (sz, sy, sx){' or (sy, sx)' if ndim == 2 else ''} (got {spacing!r})")
+        return tuple(self._fraction(v, "spacing") for v in sp)
+
+    def out_shape(self, shape, spacing):
+        shape = tuple(int(n) for n in shape)
+        if len(shape) not in (2, 3) or min(shape) < 1:
+            raise VuError(f"expected an (H,W) or (D,H,W) shape of positive lengths (got {shape})")
+        sp = self._spacing(spacing, len(shape))
+        out = []
+        for n, s, t in zip(shape, sp[3 - len(shape):], self.target[3 - len(shape):]):
+            out.append(n if t is None else max(1, math.floor(Fraction(n) * s / t + Fraction(1, 2))))
+        if math.prod(out) > 0x7fffffff:
+            raise VuError(f"the resampled shape {tuple(out)} exceeds 2^31 - 1 elements")
+        return tuple(out)
+
+    @staticmethod
+    def _to_device(t):
+        if not torch.cuda.is_available():
+            raise VuError("VolumeResampler runs on the MI355X only (no CPU fallback)")
+        return (t if t.is_cuda else t.to("cuda", non_blocking=True)).contiguous()
+
+    @staticmethod
+    def _per_item(arg, n, is_one):
+        """One argument for all n inputs, or a list of n of them."""
+        if is_one(arg):
+            return [arg] * n
+        if not isinstance(arg, (list, tuple)) or len(arg) != n:
+            raise VuError(f"expected one spacing / shape or a list of {n} of them (got {arg!r})")
+        return list(arg)
+
+    @staticmethod
+    def _is_one(arg):
+        return not isinstance(arg, (list, tuple)) or len(arg) == 0 or not isinstance(arg[0], (list, tuple))
+
+    def _resample(self, a, spacing, dtype, what, entry):
+        if isinstance(a, (list, tuple)):
+            return [self._resample(v, s, dtype, what, entry) for v, s in zip(a, self._per_item(spacing, len(a), self._is_one))]
+        v = TiledSegmenter._volume(a, dtype, what)
+        if v.numel() > 0x7fffffff:
+            raise VuError(f"{what} {tuple(v.shape)} exceeds 2^31 - 1 elements")
+        oshape = self.out_shape(tuple(v.shape), spacing)
+        v = self._to_device(v)
+        with torch.cuda.device(v.device):
+            return entry(v.reshape((-1,) + tuple(v.shape[-2:])), (1,) * (3 - len(oshape)) + oshape).reshape(oshape)
+
+    def image(self, vol, spacing):
+        return self._resample(vol, spacing, torch.int16, "volume", self.run_i16)
+
+    def labels(self, mask, spacing):
+        return self._resample(mask, spacing, torch.uint8, "mask", self.run_u8)
+
+    def logits_to(self, z, shape, truth=None, zthr: float = 0.0, label: int = -1):
+        if isinstance(z, (list, tuple)):
+            shapes = self._per_item(shape, len(z), lambda s: not isinstance(s[0], (list, tuple)))
+            truths = [None] * len(z) if truth is None else self._per_item(truth, len(z), lambda t: False)
+            return [self.logits_to(a, s, t, zthr, label) for a, s, t in zip(z, shapes, truths)]
+        if int(label) > 255:
+            raise VuError(f"label must be negative (any non-zero truth) or 0 .. 255 (got {label})")
+        if not math.isfinite(float(zthr)):
+            raise VuError(f"zthr must be a finite logit (got {zthr!r})")
+        v = TiledSegmenter._volume(z, torch.float32, "logit volume")
+        shape = tuple(int(n) for n in shape)
+        if len(shape) != v.dim() or min(shape) < 1 or math.prod(shape) > 0x7fffffff or v.numel() > 0x7fffffff:
+            raise VuError(f"cannot bring logits of shape {tuple(v.shape)} to {shape}: same rank, 1 .. 2^31 - 1 elements")
+        t = None
+        if truth is not None:
+            t = TiledSegmenter._volume(truth, torch.uint8, "truth")
+            if tuple(t.shape) != shape:
+                raise VuError(f"the truth {tuple(t.shape)} does not have the target shape {shape}")
+        v = self._to_device(v)
+        if t is not None:
+            t = t.to(v.device, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
+        with torch.cuda.device(v.device):
+            res = self.run_f32(v.reshape((-1,) + tuple(v.shape[-2:])), (1,) * (3 - len(shape)) + shape, t, float(zthr), int(label))
+        return {k: (a if k == "counts" else a.reshape(shape)) for k, a in res.items()}
+
+    # ---- one launch each on (D,H,W) device tensors
+    @staticmethod
+    def run_i16(vol: torch.Tensor, oshape) -> torch.Tensor:
+        out = torch.empty(oshape, dtype=torch.int16, device=vol.device)
+        check(lib().vu_resample_i16(ptr(vol), ptr(out), *(int(n) for n in vol.shape), *oshape, stream_ptr(vol.device)), "vu_resample_i16")
+        return out
+
+    @staticmethod
+    def run_u8(mask: torch.Tensor, oshape) -> torch.Tensor:
+        out = torch.empty(oshape, dtype=torch.uint8, device=mask.device)
+        check(lib().vu_resample_u8_nearest(ptr(mask), ptr(out), *(int(n) for n in mask.shape), *oshape, stream_ptr(mask.device)),
+              "vu_resample_u8_nearest")
+        return out
+
+    @staticmethod
+    def run_f32(z: torch.Tensor, oshape, truth=None, zthr: float = 0.0, label: int = -1, logits: bool = True, mask: bool = True):
+        """One vu_resample_f32: {"logits" and / or "mask" of `oshape` and, with a truth, "counts" (Do,3) int64}, on the device."""
+        L, dev = lib(), z.device
+        Do, Ho, Wo = (int(n) for n in oshape)
+        res = {}
+        if logits:
+            res["logits"] = torch.empty(Do, Ho, Wo, dtype=torch.float32, device=dev)
+        if mask:
+            res["mask"] = torch.empty(Do, Ho, Wo, dtype=torch.uint8, device=dev)
+        scratch, nbytes = None, 0
+        if truth is not None:
+            res["counts"] = torch.empty(Do, 3, dtype=torch.int64, device=dev)
+            nbytes = int(L.vu_resample_f32_scratch_bytes(Do, Ho, Wo))
+            scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+        check(L.vu_resample_f32(ptr(z), ptr(truth), ptr(res.get("logits")), ptr(res.get("mask")), ptr(res.get("counts")), ptr(scratch),
+                                nbytes, *(int(n) for n in z.shape), Do, Ho, Wo, float(zthr), int(label), stream_ptr(dev)),
+              "vu_resample_f32")
+        return res
+
+
 class TiledSegmenter:
     """`s = TiledSegmenter(model, overlap=32, batch=64); mask = s(vol)`.
 
@@ -381,10 +543,19 @@ class TiledSegmenter:
 
     `surface`: a `SurfaceDistance`.  `score` then runs one `vu_surface_dist` on the final mask (after `clean`, if given)
     against the truth under `label` and adds "surface": the dict of `SurfaceDistance.score`.  `surface=None` launches nothing
-    new and returns exactly the dicts above."""
+    new and returns exactly the dicts above.
+
+    `resample`: a `VolumeResampler` (or the target spacing of one).  `s(vol, output, spacing=)` and `s.score(vol, truth,
+    spacing=)` then take the volume's own voxel size (sz, sy, sx) and run the model at the working spacing: one
+    `vu_resample_i16` brings the volume to `resample.out_shape(vol.shape, spacing)`, the order above runs there for the
+    logits, and one `vu_resample_f32` brings them back to the volume's own shape, where they are thresholded and - in
+    `score` - counted against the native truth; `clean` and `surface` then work on that native-grid mask as before, and
+    "logits" / "prob" are native-grid values.  A list of volumes takes one spacing for all or a list of them.  A resampler
+    without a spacing and a spacing without a resampler are refused; `resample=None` launches nothing new and returns today's
+    results bit for bit."""
 
     def __init__(self, model, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
-                 label: int = -1, ensemble: int = 1, clean=None, surface=None):
+                 label: int = -1, ensemble: int = 1, clean=None, surface=None, resample=None):
         T = int(model.im_size)
         if int(model.num_channels) != 1:
             raise VuError(f"a segmentation model has 1 channel (this one has {model.num_channels})")
@@ -403,7 +574,9 @@ class TiledSegmenter:
             raise VuError(f"clean must be a MaskCleaner or None (got {type(clean).__name__})")
         if surface is not None and not isinstance(surface, SurfaceDistance):
             raise VuError(f"surface must be a SurfaceDistance or None (got {type(surface).__name__})")
-        self.clean, self.surface = clean, surface
+        if resample is not None and not isinstance(resample, VolumeResampler):
+            resample = VolumeResampler(resample)
+        self.clean, self.surface, self.resample = clean, surface, resample
         self.zthr = logit_threshold(threshold)
         self.model, self.T, self.overlap, self.batch = model, T, int(overlap), int(batch)
         self.window, self.threshold, self.label, self.ensemble = (lo, hi), float(threshold), int(label), int(ensemble)
@@ -424,40 +597,64 @@ class TiledSegmenter:
             raise VuError(f"empty {what} {tuple(t.shape)}")
         return t
 
-    def __call__(self, vol, output: str = "mask"):
+    def __call__(self, vol, output: str = "mask", spacing=None):
         if isinstance(vol, (list, tuple)):
-            return [self(v, output) for v in vol]
+            if spacing is None:
+                return [self(v, output) for v in vol]
+            return [self(v, output, s) for v, s in zip(vol, VolumeResampler._per_item(spacing, len(vol), VolumeResampler._is_one))]
         if output not in ("mask", "logits", "prob"):
             raise VuError(f"output must be 'mask', 'logits' or 'prob' (got {output!r})")
         if self.clean is not None and output != "mask":
             raise VuError(f"a cleaner works on the mask: output={output!r} with clean= is refused")
         v = self._volume(vol, torch.int16, "volume")
         self._check_clean(v)
+        wshape = self._working_shape(tuple(v.shape), spacing)
         dev = self._device()
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
         with torch.no_grad():
             if output == "mask":
-                m = self._run(v, None, mask=True)["mask"]
+                m = (self._run(v, None, mask=True) if wshape is None else self._run_resampled(v, wshape, None, mask=True))["mask"]
                 if self.clean is not None:
                     m = self.clean.run(m, None, out=m)["mask"]
                 return m.reshape(shape)
-            z = self._run(v, None, logits=True)["logits"].reshape(shape)
+            z = (self._run(v, None, logits=True) if wshape is None else self._run_resampled(v, wshape, None, logits=True))["logits"]
+            z = z.reshape(shape)
             return z if output == "logits" else torch.sigmoid(z)
 
-    def score(self, vol, truth):
+    def _working_shape(self, shape, spacing):
+        """None without a resampler; else the (D,H,W) working-grid shape of a volume of `shape` and `spacing`."""
+        if self.resample is None:
+            if spacing is not None:
+                raise VuError("a spacing= needs a resampler: TiledSegmenter(..., resample=VolumeResampler(...))")
+            return None
+        if spacing is None:
+            raise VuError("this segmenter resamples to a working spacing: give the volume's own spacing=(sz, sy, sx)")
+        w = self.resample.out_shape(shape, spacing)
+        return (1,) * (3 - len(w)) + w
+
+    def _run_resampled(self, vol: torch.Tensor, wshape, truth, logits: bool = False, mask: bool = False):
+        """`_run` at the working spacing: vu_resample_i16 to `wshape`, the logits there, one vu_resample_f32 back to vol's
+        shape -> what `_run` returns, on the native grid."""
+        with torch.cuda.device(vol.device):
+            work = VolumeResampler.run_i16(vol, wshape)
+            z = self._run(work, None, logits=True)["logits"]
+            return VolumeResampler.run_f32(z, tuple(vol.shape), truth, self.zthr, self.label, logits=logits, mask=mask)
+
+    def score(self, vol, truth, spacing=None):
         v, t = self._volume(vol, torch.int16, "volume"), self._volume(truth, torch.uint8, "truth")
         if tuple(v.shape) != tuple(t.shape):
             raise VuError(f"the truth {tuple(t.shape)} does not have the volume's shape {tuple(v.shape)}")
         self._check_clean(v)
         if self.surface is not None:
             self.surface._check_shape(tuple(v.shape))
+        wshape = self._working_shape(tuple(v.shape), spacing)
         dev = self._device()
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
         t = t.to(dev, non_blocking=True).contiguous().reshape(v.shape)
         with torch.no_grad():
-            res = self._run(v, t, mask=True)
+            res = self._run(v, t, mask=True) if wshape is None else self._run_resampled(v, wshape, t, mask=True)
             if self.clean is not None:
                 raw = res["counts"].cpu()
                 out = MaskCleaner.finish(self.clean.run(res["mask"], t, self.label, out=res["mask"]), shape)
