@@ -508,6 +508,40 @@ size_t vu_resample_f32_scratch_bytes(int Do, int Ho, int Wo);
 int vu_resample_f32(const float* in, const uint8_t* truth, float* out, uint8_t* mask, unsigned long long* counts, void* scratch,
                     size_t scratch_bytes, int Di, int Hi, int Wi, int Do, int Ho, int Wo, float zthr, int label, void* stream);
 
+/* ---- Per-volume intensity statistics (csrc/vu_intensity.hip; Python: segment.IntensityNormalizer) ----
+ * The exact histogram of an int16 volume under a voxel selection, the bounding box of the selected voxels, and the integers a
+ * per-volume intensity window is made of.  No float arithmetic anywhere; integer atomics only, whose result does not depend on
+ * order: every output is the same bits on every run.
+ *   intensity_hist   vol (D,H,W) int16, D H W < 2^32.  hist: 65536 uint32 in device memory; afterwards hist[b] is the number of
+ *                    selected voxels with value b - 32768.  The call clears hist itself (stale contents do not matter).  select:
+ *                      0  every voxel
+ *                      1  voxels with v > floor (strict; the MR "non-air" rule is floor = 0; any int is accepted)
+ *                      2  the foreground voxels of mask (D,H,W) uint8 under the label rule of vu_seg_blend: mask != 0 when
+ *                         label < 0, mask == label when 0 .. 255.  mask is read for select 2 only.
+ *                    bbox: NULL, or 6 int32 in device memory (z0, z1, y0, y1, x0, x1), the inclusive extent of the selected
+ *                    voxels; (D, -1, H, -1, W, -1) when none is selected.  Two launches: one clears hist and bbox, one counts.
+ *                    A vol that is 16-byte aligned (and, for select 2, a mask that is 8-byte aligned) is read 8 voxels per lane,
+ *                    anything else by scalar loads; the last partial chunk always by scalar loads.
+ *   intensity_rank   the rank arithmetic alone, host code without a GPU call: for 1 <= N < 2^32, 0 <= pn <= pd, 1 <= pd <= 10^6,
+ *                    k = ((N - 1) pn) div pd and r = ((N - 1) pn) mod pd; the product is < 2^52.
+ *   intensity_stats  one launch of a fixed geometry over hist.  stats: (8 + 4 nq) int64 in device memory, 0 <= nq <= 4:
+ *                      [0] N = the number of selected voxels, [1] min, [2] max, [3] sum of v, [4] sum of v^2 (< 2^62), [5..7] 0
+ *                      [8 + 4 j ..] for quantile j = pn[j] / pd[j] (a fraction of 1): k, r as intensity_rank gives them for N, the
+ *                      k-th smallest selected value (counted from 0) and the min(k + 1, N - 1)-th smallest.
+ *                    With N = 0 every entry but [0] is 0.  pn and pd are HOST arrays of nq entries, read during the call.  N is
+ *                    read on the device: the call does not wait for the device.
+ *   intensity_geometry   what the histogram kernel was built with: values lds_base .. lds_base + lds_bins - 1 are counted in a
+ *                    private LDS sub-histogram per workgroup (lds_bins = 0: the direct measurement form), everything else by
+ *                    global atomics; a workgroup takes voxels_per_block voxels per step of its grid-stride loop.
+ * Refused before any launch (VU_EINVAL): a null vol, hist or stats (and pn / pd with nq > 0, k / r, a geometry pointer); select
+ * outside 0 .. 2; select 2 without a mask; label > 255; a dimension < 1 or D H W >= 2^32; hist or bbox not 4-byte aligned, stats
+ * not 8-byte aligned; nq outside 0 .. 4; N, pn or pd outside the ranges of intensity_rank. */
+int vu_intensity_geometry(int* lds_base, int* lds_bins, int* voxels_per_block);
+int vu_intensity_hist(const int16_t* vol, const uint8_t* mask, uint32_t* hist, int32_t* bbox, int D, int H, int W, int select, int floor,
+                      int label, void* stream);
+int vu_intensity_rank(unsigned long long N, unsigned pn, unsigned pd, unsigned long long* k, unsigned* r);
+int vu_intensity_stats(const uint32_t* hist, const unsigned* pn, const unsigned* pd, int nq, long long* stats, void* stream);
+
 /* ---- ops of the reference's Keras re-implementation (csrc/vu_tfops.hip).  Not on the benchmarked path.
  * n % 4 == 0 everywhere; dropout masks replay from (seed, stream_id) with element index = linear index (vu_dropout) or
  * row * ld + j (softmax rows), as every other dropout site of this library. ---- */

@@ -141,6 +141,10 @@ SIGNATURES = {
     "vu_resample_u8_nearest": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "vu_resample_f32_scratch_bytes": (_sz, [_i, _i, _i]),
     "vu_resample_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "vu_intensity_geometry": (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "vu_intensity_hist": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "vu_intensity_rank": (_i, [C.c_ulonglong, C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]),
+    "vu_intensity_stats": (_i, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _i, _vp, _vp]),
     "vu_dihedral_inverse": (_i, [_i]),
     "vu_patch_pairs_u8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _f, _vp]),
     "vu_dihedral_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),

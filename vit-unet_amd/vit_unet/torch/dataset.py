@@ -248,6 +248,9 @@ class SegmentationPatchTransform:
     `train=False` is ONE centred crop of the middle slice (z = D//2, y0 = (H-T)//2, x0 = (W-T)//2) with op 0 and launches no
     draw.  `crops=` - one (per_volume,4) integer table (z, y0, x0, op) per volume - replaces the draw and is checked on the
     host.  `last_crops` keeps the device tables of the last call (a list, one (per_volume,4) int32 tensor per volume).
+    `window` may be a `segment.IntensityNormalizer` instead of a (lo, hi) pair: every volume of a call is then measured (its mask
+    is the mask of select "mask"), which waits for the device once per volume; `windows=` - one (lo, hi) per volume, e.g. measured
+    once before training - replaces the measurement (or the constructor's pair): no statistics launch and no wait.
     Argument errors raise `VuError` before any launch (the cut itself clamps what it is given)."""
 
     def __init__(self, patch: int = 224, per_volume: int = 8, train: bool = True, window=(-1024.0, 1024.0), ls: float = 0.0,
@@ -258,16 +261,16 @@ class SegmentationPatchTransform:
             raise VuError(f"patch and per_volume must be at least 1 (got {patch}, {per_volume})")
         if self.patch > 65535:
             raise VuError(f"a patch has at most 65535 pixels a side (got {patch})")
-        lo, hi = float(np.float32(window[0])), float(np.float32(window[1]))
-        if not hi > lo:
-            raise VuError(f"the intensity window must have hi > lo (got {window[0]} .. {window[1]})")
+        from .segment import IntensityNormalizer, window_pair
+        self.normalizer = window if isinstance(window, IntensityNormalizer) else None
+        lo_hi = None if self.normalizer is not None else window_pair(window)
         if not 0.0 <= float(ls) < 1.0:
             raise VuError(f"label smoothing must be in [0,1) (got {ls})")
         if not 0.0 <= float(fg) <= 1.0:
             raise VuError(f"fg, the share of foreground crops, must be in [0,1] (got {fg})")
         if int(label) > 255:
             raise VuError(f"label must be negative (any non-zero mask value) or 0 .. 255 (got {label})")
-        self.window, self.ls, self.fg, self.label, self.device = (lo, hi), float(ls), float(fg), int(label), device
+        self.window, self.ls, self.fg, self.label, self.device = lo_hi, float(ls), float(fg), int(label), device
         self.rng = random.Random(seed)
         self.last_crops: Optional[List[torch.Tensor]] = None
 
@@ -305,7 +308,7 @@ class SegmentationPatchTransform:
             raise VuError(f"crops[{b}] leaves the volume ({D} x {H} x {W}, patch {T}) or names an op outside 0 .. 7")
         return np.ascontiguousarray(t, dtype=np.int32)
 
-    def __call__(self, image, mask, crops=None) -> Dict[str, torch.Tensor]:
+    def __call__(self, image, mask, crops=None, windows=None) -> Dict[str, torch.Tensor]:
         vs, ms = self._volumes(image, torch.int16, "volume"), self._volumes(mask, torch.uint8, "mask")
         if len(vs) != len(ms):
             raise VuError(f"{len(vs)} volumes and {len(ms)} masks")
@@ -327,13 +330,19 @@ class SegmentationPatchTransform:
             tables = [self._check_table(c, b, shapes[b]) for b, c in enumerate(crops)]
         elif not self.train:
             tables = [np.array([[D // 2, (H - T) // 2, (W - T) // 2, 0]], dtype=np.int32) for D, H, W in shapes]
+        if windows is not None:
+            from .segment import window_pair
+            if not isinstance(windows, (list, tuple)) or len(windows) != B:
+                raise VuError(f"windows must hold one (lo, hi) per volume ({B})")
+            windows = [window_pair(w, f"windows[{b}]") for b, w in enumerate(windows)]
         if not str(self.device).startswith("cuda"):
             raise VuError("SegmentationPatchTransform runs on the MI355X only (device 'cuda'; no CPU fallback)")
         vs = [v.to(self.device, non_blocking=True).contiguous() for v in vs]
         ms = [m.to(self.device, non_blocking=True).contiguous() for m in ms]
         dev = vs[0].device
         L, st = lib(), stream_ptr(dev)
-        lo, hi = self.window
+        if windows is None:
+            windows = [self.window] * B if self.normalizer is None else [self.normalizer.window(vs[b], ms[b]) for b in range(B)]
         x = torch.empty(B * P, 1, T, T, dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
         self.last_crops = []
@@ -350,6 +359,7 @@ class SegmentationPatchTransform:
                 check(L.vu_segpatch_draw(ptr(ms[b]), ptr(index), ptr(words), ptr(d), P, D, H, W, T, self.fg_thresh, self.label, st),
                       "vu_segpatch_draw")
             self.last_crops.append(d)
+            lo, hi = windows[b]
             check(L.vu_patch_pairs_i16(ptr(vs[b]), ptr(ms[b]), ptr(x[b * P:(b + 1) * P]), ptr(y[b * P:(b + 1) * P]), D, H, W, T, ptr(d),
                                        P, lo, hi, self.ls, self.label, st), "vu_patch_pairs_i16")
         return {"x": x, "y": y}

@@ -114,7 +114,9 @@ def dice_tiled(model, pairs, overlap: int = 32, batch: int = 64, window=(-1024.0
     integer counts of the whole volume (1.0 when mask and truth are both empty).  `clean`: a segment.MaskCleaner applied to
     the thresholded mask before it is counted.  `resample`: a segment.VolumeResampler (or its target spacing); the items are
     then (volume, truth, spacing) triples, the model runs at the working spacing and the mask is counted on the volume's own
-    grid (see `TiledSegmenter`).  None launches nothing new."""
+    grid (see `TiledSegmenter`).  None launches nothing new.  `window`: a (lo, hi) pair for all volumes, or a
+    segment.IntensityNormalizer, which measures every volume before its inference pass (with select "mask" the truth is the
+    mask); the same holds for `iou_tiled`, `hd95_tiled`, `assd_tiled` and `nsd_tiled`."""
     return _tiled_overlap(model, pairs, "dice", overlap=overlap, batch=batch, window=window, threshold=threshold, label=label,
                           ensemble=ensemble, clean=clean, resample=resample)
 

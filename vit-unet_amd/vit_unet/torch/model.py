@@ -707,8 +707,9 @@ class HViT_UNet(nn.Module):
         """Label mask of a whole int16 slice (H,W) or volume (D,H,W) of any size by sliding-window inference
         (segment.TiledSegmenter, built once per set of its keyword arguments - overlap, batch, window, threshold, label,
         ensemble, clean, surface, resample - and kept).  With `resample=` (a segment.VolumeResampler or its target spacing)
-        `spacing` is the volume's own voxel size and the model runs at the working spacing.  `forward` is unchanged: it still
-        resizes inputs of another size."""
+        `spacing` is the volume's own voxel size and the model runs at the working spacing.  `window=` is a (lo, hi) pair or a
+        segment.IntensityNormalizer, which measures every volume of a call.  `forward` is unchanged: it still resizes inputs of
+        another size."""
         from .segment import TiledSegmenter
         key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in kw.items()))
         cache = self.__dict__.setdefault("_segmenters", {})

@@ -111,9 +111,10 @@ class VolumeLoader:
     """`BatchLoader` for volumes whose sizes may differ: lists of (D,H,W) int16 volumes and uint8 label masks -> {'x','y'}
     patch batches via a `SegmentationPatchTransform`, `per_step` volumes a batch.  Re-iterable (one pass per epoch)."""
 
-    def __init__(self, volumes, truths, idx: Sequence[int], per_step: int, transform, shuffle: bool, seed: int = 0):
+    def __init__(self, volumes, truths, idx: Sequence[int], per_step: int, transform, shuffle: bool, seed: int = 0, windows=None):
         self.volumes, self.truths, self.idx, self.bs, self.tf, self.shuffle = volumes, truths, np.asarray(idx), per_step, transform, shuffle
         self.rs = np.random.RandomState(seed)
+        self.windows = windows      # one (lo, hi) per volume, measured beforehand: the transform then measures nothing
 
     def __len__(self):
         return (len(self.idx) + self.bs - 1) // self.bs
@@ -122,7 +123,10 @@ class VolumeLoader:
         order = self.rs.permutation(self.idx) if self.shuffle else self.idx
         for i in range(0, len(order), self.bs):
             sel = order[i:i + self.bs]
-            yield self.tf([self.volumes[k] for k in sel], [self.truths[k] for k in sel])
+            if self.windows is None:
+                yield self.tf([self.volumes[k] for k in sel], [self.truths[k] for k in sel])
+            else:
+                yield self.tf([self.volumes[k] for k in sel], [self.truths[k] for k in sel], windows=[self.windows[k] for k in sel])
 
 
 def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_string: str = "lite", lr: float = 1e-4,
@@ -143,7 +147,11 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
     `spacings` (one (sz, sy, sx) voxel size per volume) and `resample` (a segment.VolumeResampler or its target spacing), given
     together: every volume and its truth are resampled once on the device to the working spacing (trilinear / nearest) and the
     training and validation patches are cut from those (every resampled slice at least im_size x im_size); the test volumes are
-    scored on their own grids by `TiledSegmenter(resample=)`.  Without them nothing changes."""
+    scored on their own grids by `TiledSegmenter(resample=)`.  Without them nothing changes.
+    `window`: a (lo, hi) pair or a segment.IntensityNormalizer.  A normalizer measures every volume ONCE, before the folds, as
+    passed (on its own grid; with select "mask" its truth is the mask); the stored windows then serve the training patches, the
+    validation crops and the scoring of that volume, so the epoch loop launches no statistics and never waits on their account.
+    The result gains 'windows', the list of (lo, hi)."""
     assert len(volumes) == len(truths), f"{len(volumes)} volumes and {len(truths)} truths"
     assert (spacings is None) == (resample is None), "spacings= and resample= go together"
     work_volumes, work_truths = volumes, truths
@@ -156,6 +164,8 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
         work_truths = resample.labels(list(truths), [tuple(s) for s in spacings])
     assert crops_per_volume >= 1 and batch_size % crops_per_volume == 0, \
         f"batch_size {batch_size} (patches) must be a multiple of crops_per_volume {crops_per_volume}"
+    from .segment import IntensityNormalizer
+    windows = window.window(list(volumes), list(truths)) if isinstance(window, IntensityNormalizer) else None
     results, histories = [], []
     surf = {"hd95": [], "assd": [], "nsd": []}
     for fold, (train_idx, test_idx) in enumerate(kfold_indices(len(volumes), folds, seed)):
@@ -163,9 +173,10 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
             print(f"FOLD {fold}: Training on {len(train_idx)} volumes and testing on {len(test_idx)} volumes")
         train = VolumeLoader(work_volumes, work_truths, train_idx, batch_size // crops_per_volume,
                              SegmentationPatchTransform(im_size, crops_per_volume, train=True, window=window, ls=ls, fg=fg, label=label,
-                                                        seed=seed + fold), shuffle=True, seed=seed + fold)
+                                                        seed=seed + fold), shuffle=True, seed=seed + fold, windows=windows)
         test = VolumeLoader(work_volumes, work_truths, test_idx, batch_size,
-                            SegmentationPatchTransform(im_size, train=False, window=window, ls=ls, label=label), shuffle=False)
+                            SegmentationPatchTransform(im_size, train=False, window=window, ls=ls, label=label), shuffle=False,
+                            windows=windows)
         model = models.get_vit_unet(model_string, dtype=dtype, **{**(model_kwargs or {}), "num_channels": 1, "im_size": im_size})
         model.to("cuda")
         optimizer = torch.optim.AdamW(model.parameters(), lr=lr)
@@ -175,26 +186,29 @@ def run_segmentation(volumes, truths, n_epochs: int = 5, folds: int = 5, model_s
         fitter.load(os.path.join(folder, "best-checkpoint.bin"))
         model = fitter.model
         model.eval()
-        if surface is None and resample is None:
+        if surface is None and resample is None and windows is None:
             score = fn.dice_tiled(model, ((volumes[i], truths[i]) for i in test_idx), overlap=min(32, im_size // 2), window=window,
                                   label=label, ensemble=ensemble, clean=clean)
-        elif surface is None:
+        elif surface is None and windows is None:
             score = fn.dice_tiled(model, ((volumes[i], truths[i], tuple(spacings[i])) for i in test_idx), overlap=min(32, im_size // 2),
                                   window=window, label=label, ensemble=ensemble, clean=clean, resample=resample)
-        else:   # one inference pass per volume for Dice and the boundary metrics
+        else:   # one inference pass per volume for Dice and the boundary metrics, under the volume's stored window if measured
             from .segment import TiledSegmenter
             seg = TiledSegmenter(model, overlap=min(32, im_size // 2), window=window, label=label, ensemble=ensemble, clean=clean,
                                  surface=surface, resample=resample)
-            scored = [seg.score(volumes[i], truths[i], **({} if resample is None else {"spacing": tuple(spacings[i])}))
-                      for i in test_idx]
+            scored = [seg.score(volumes[i], truths[i], **({} if resample is None else {"spacing": tuple(spacings[i])}),
+                                **({} if windows is None else {"window": windows[i]})) for i in test_idx]
             score = np.array([r["dice"] for r in scored], dtype=np.float64)
-            for k in surf:
-                surf[k].append(np.array([r["surface"][k] for r in scored], dtype=np.float64))
+            if surface is not None:
+                for k in surf:
+                    surf[k].append(np.array([r["surface"][k] for r in scored], dtype=np.float64))
         if verbose:
             print(f"FOLD {fold}: Mean Dice {np.mean(score)}")
         results.append(score)
     allv = np.concatenate([np.asarray(r, dtype=np.float64).reshape(-1) for r in results])
     out = {"dice": results, "dice_mean": float(allv.mean()), "dice_std": float(allv.std()), "history": histories}
+    if windows is not None:
+        out["windows"] = windows
     if surface is not None:
         for k, v in surf.items():
             a = np.concatenate(v)

@@ -22,6 +22,11 @@ them.
 before patches and windows, and logits are brought back to the volume's own grid before the threshold (csrc/vu_resample.hip,
 C ABI `vu_resample_i16`, `vu_resample_u8_nearest`, `vu_resample_f32`); `TiledSegmenter(resample=VolumeResampler(...))` does
 both around the model and thresholds, cleans, counts and measures on the native grid.
+
+`IntensityNormalizer` replaces the fixed intensity window by one measured per volume: the exact int16 histogram of the volume
+(all voxels, those above a floor, or those of a mask) on the device, and from its integers a percentile or mean +- k std window
+formed on the host in exact rational arithmetic (csrc/vu_intensity.hip, C ABI `vu_intensity_hist`, `vu_intensity_stats`).
+Every `window=` of this package that takes a (lo, hi) pair also takes one.
 """
 from __future__ import annotations
 
@@ -516,6 +521,163 @@ class VolumeResampler:
         return res
 
 
+class IntensityNormalizer:
+    """`n = IntensityNormalizer(mode="percentile", lo=0.5, hi=99.5, k=3.0, select="all", floor=0, label=-1); lo, hi = n.window(vol)`.
+
+    A per-volume intensity window for volumes without an absolute scale (MR): x = clip((v - lo) / (hi - lo), 0, 1) with lo, hi
+    measured on the volume itself.  `select` names the voxels that are measured: "all"; "above": v > `floor` (strict; floor 0 is
+    the MR non-air rule); "mask": the foreground of the `mask` argument under `label` (mask != 0 when label < 0, mask == label
+    when 0 .. 255).  The histogram (65536 bins, exact) and every integer come from the device (csrc/vu_intensity.hip; contract
+    in include/vit_unet_amd.h); the window is formed on the host from those integers alone, in `fractions.Fraction` arithmetic, so
+    it is a function of the volume and of nothing else:
+      mode "percentile"  the `lo` and `hi` percentiles (percent, rounded to 1e-4 percent: pn = round(p 10^4), pd = 10^6) under
+                         numpy's linear definition, q = v_k + (v_k1 - v_k) r / pd exactly, rounded once to float64, then to float32
+      mode "zscore"      mean = sum / N and var = (N sumsq - sum^2) / N^2 exactly; std = math.sqrt(float(var));
+                         lo / hi = float32(float(mean) -+ k std): x is the z-score clipped at +-k and mapped to [0, 1]
+    If hi > lo does not hold after rounding (a constant volume, N = 1), hi = lo + 1.  An empty selection raises `VuError`.
+      n.hist(vol, mask=None)    the device histogram, (65536,) int64 (hist[b] counts the value b - 32768)
+      n.stats(vol, mask=None)   {"n", "min", "max", "sum", "sumsq" (exact ints), "mean", "std" (host floats; None when n = 0),
+                                "quantiles": [(k, r, v_k, v_k1) for lo and hi]}
+      n.bbox(vol, mask=None)    (z0, z1, y0, y1, x0, x1), the inclusive extent of the selected voxels ((D, -1, H, -1, W, -1) when none;
+                                an (H,W) input counts as D = 1)
+      n.window(vol, mask=None)  (lo, hi): Python floats that are exactly float32 values
+    vol is (H,W) or (D,H,W) int16, mask uint8 of the same shape (needed for select "mask" only); numpy or torch, host or device; a
+    list / tuple of volumes gives a list.  `window` and `stats` cost three small launches (clear, count, statistics) and one
+    128-byte read-back: they wait for the device once per volume - measure a volume once and keep the numbers (`run_segmentation`
+    does).  No CPU fallback: inputs are moved to 'cuda'.  Argument errors raise `VuError` before any launch."""
+
+    SELECT = {"all": 0, "above": 1, "mask": 2}
+    PD = 10 ** 6
+
+    def __init__(self, mode: str = "percentile", lo: float = 0.5, hi: float = 99.5, k: float = 3.0, select: str = "all",
+                 floor: int = 0, label: int = -1):
+        num = (int, float, np.integer, np.floating)
+        if mode not in ("percentile", "zscore"):
+            raise VuError(f"mode must be 'percentile' or 'zscore' (got {mode!r})")
+        if any(isinstance(p, bool) or not isinstance(p, num) for p in (lo, hi)) or not 0.0 <= float(lo) < float(hi) <= 100.0:
+            raise VuError(f"lo and hi are percentages with 0 <= lo < hi <= 100 (got {lo!r}, {hi!r})")
+        if isinstance(k, bool) or not isinstance(k, num) or not math.isfinite(float(k)) or float(k) <= 0.0:
+            raise VuError(f"k must be a finite number > 0 (got {k!r})")
+        if select not in self.SELECT:
+            raise VuError(f"select must be one of {sorted(self.SELECT)} (got {select!r})")
+        if isinstance(floor, bool) or not isinstance(floor, (int, np.integer)) or not -2 ** 31 <= int(floor) < 2 ** 31:
+            raise VuError(f"floor must be an integer that fits int32 (got {floor!r})")
+        if isinstance(label, bool) or not isinstance(label, (int, np.integer)) or not -2 ** 31 <= int(label) <= 255:
+            raise VuError(f"label must be negative (any non-zero mask value) or 0 .. 255 (got {label!r})")
+        self.mode, self.lo, self.hi, self.k = mode, float(lo), float(hi), float(k)
+        self.select, self.floor, self.label = select, int(floor), int(label)
+        self.pn = (int(round(self.lo * 10 ** 4)), int(round(self.hi * 10 ** 4)))
+
+    @staticmethod
+    def _to_device(t):
+        if not torch.cuda.is_available():
+            raise VuError("IntensityNormalizer runs on the MI355X only (no CPU fallback)")
+        return (t if t.is_cuda else t.to("cuda", non_blocking=True)).contiguous()
+
+    def _inputs(self, vol, mask):
+        """(vol, mask or None) as (D,H,W) device tensors."""
+        v = TiledSegmenter._volume(vol, torch.int16, "volume")
+        if v.numel() >= 2 ** 32:
+            raise VuError(f"volume {tuple(v.shape)} has 2^32 voxels or more")
+        m = None
+        if self.select == "mask":
+            if mask is None:
+                raise VuError("select='mask' measures the foreground of a mask: pass mask=")
+            m = TiledSegmenter._volume(mask, torch.uint8, "mask")
+            if tuple(m.shape) != tuple(v.shape):
+                raise VuError(f"the mask {tuple(m.shape)} does not have the volume's shape {tuple(v.shape)}")
+        v = self._to_device(v)
+        v = v.reshape((-1,) + tuple(v.shape[-2:]))
+        if m is not None:
+            m = m.to(v.device, non_blocking=True).contiguous().reshape(v.shape)
+        return v, m
+
+    # ---- the launches, on (D,H,W) device tensors
+    def run_hist(self, vol: torch.Tensor, mask=None, bbox: bool = False):
+        """vu_intensity_hist: (hist (65536,) int32 holding the uint32 bits, bbox (6,) int32 or None), on the device."""
+        dev = vol.device
+        hist = torch.empty(65536, dtype=torch.int32, device=dev)
+        box = torch.empty(6, dtype=torch.int32, device=dev) if bbox else None
+        check(lib().vu_intensity_hist(ptr(vol), ptr(mask), ptr(hist), ptr(box), *(int(n) for n in vol.shape), self.SELECT[self.select],
+                                      self.floor, self.label, stream_ptr(dev)), "vu_intensity_hist")
+        return hist, box
+
+    def run_stats(self, hist: torch.Tensor) -> torch.Tensor:
+        """vu_intensity_stats with the lo and hi quantiles: (16,) int64 on the device."""
+        stats = torch.empty(16, dtype=torch.int64, device=hist.device)
+        pn, pd = (C.c_uint * 2)(*self.pn), (C.c_uint * 2)(self.PD, self.PD)
+        check(lib().vu_intensity_stats(ptr(hist), pn, pd, 2, ptr(stats), stream_ptr(hist.device)), "vu_intensity_stats")
+        return stats
+
+    def _measure(self, vol, mask):
+        v, m = self._inputs(vol, mask)
+        with torch.cuda.device(v.device):
+            return [int(x) for x in self.run_stats(self.run_hist(v, m)[0]).cpu().tolist()]
+
+    # ---- the public calls
+    def hist(self, vol, mask=None):
+        if isinstance(vol, (list, tuple)):
+            return [self.hist(v, m) for v, m in zip(vol, mask if mask is not None else [None] * len(vol))]
+        v, m = self._inputs(vol, mask)
+        with torch.cuda.device(v.device):
+            return self.run_hist(v, m)[0].to(torch.int64) & 0xffffffff
+
+    def bbox(self, vol, mask=None):
+        if isinstance(vol, (list, tuple)):
+            return [self.bbox(v, m) for v, m in zip(vol, mask if mask is not None else [None] * len(vol))]
+        v, m = self._inputs(vol, mask)
+        with torch.cuda.device(v.device):
+            return tuple(int(x) for x in self.run_hist(v, m, bbox=True)[1].cpu().tolist())
+
+    def stats(self, vol, mask=None):
+        if isinstance(vol, (list, tuple)):
+            return [self.stats(v, m) for v, m in zip(vol, mask if mask is not None else [None] * len(vol))]
+        return self.stats_dict(self._measure(vol, mask))
+
+    def window(self, vol, mask=None):
+        if isinstance(vol, (list, tuple)):
+            return [self.window(v, m) for v, m in zip(vol, mask if mask is not None else [None] * len(vol))]
+        return self.window_from(self._measure(vol, mask))
+
+    # ---- host arithmetic on the 16 integers of `run_stats`
+    @staticmethod
+    def stats_dict(st) -> dict:
+        n, s, s2 = int(st[0]), int(st[3]), int(st[4])
+        out = {"n": n, "min": int(st[1]), "max": int(st[2]), "sum": s, "sumsq": s2, "mean": None, "std": None,
+               "quantiles": [tuple(int(x) for x in st[8 + 4 * j:12 + 4 * j]) for j in range(2)]}
+        if n:
+            out["mean"] = float(Fraction(s, n))
+            out["std"] = math.sqrt(float(Fraction(n * s2 - s * s, n * n)))
+        return out
+
+    def window_from(self, st):
+        """(lo, hi) from the 16 integers (N, min, max, sum, sumsq, 0, 0, 0, then k, r, v_k, v_k1 for lo and for hi)."""
+        n = int(st[0])
+        if n == 0:
+            raise VuError(f"the selection ({self.select!r}) is empty: no voxel to measure the intensity window on")
+        if self.mode == "percentile":
+            lo, hi = (float(np.float32(float(Fraction(int(st[10 + 4 * j])) +
+                                             Fraction((int(st[11 + 4 * j]) - int(st[10 + 4 * j])) * int(st[9 + 4 * j]), self.PD))))
+                      for j in range(2))
+        else:
+            d = self.stats_dict(st)
+            lo, hi = float(np.float32(d["mean"] - self.k * d["std"])), float(np.float32(d["mean"] + self.k * d["std"]))
+        if not hi > lo:
+            hi = float(np.float32(lo + 1.0))
+        return lo, hi
+
+
+def window_pair(window, what: str = "the intensity window"):
+    """A (lo, hi) window as two Python floats that are float32 values; hi > lo or VuError."""
+    try:
+        lo, hi = float(np.float32(window[0])), float(np.float32(window[1]))
+    except (TypeError, IndexError, ValueError):
+        raise VuError(f"{what} must be a (lo, hi) pair or an IntensityNormalizer (got {window!r})") from None
+    if not hi > lo:
+        raise VuError(f"{what} must have hi > lo (got {window[0]} .. {window[1]})")
+    return lo, hi
+
+
 class TiledSegmenter:
     """`s = TiledSegmenter(model, overlap=32, batch=64); mask = s(vol)`.
 
@@ -552,7 +714,13 @@ class TiledSegmenter:
     `score` - counted against the native truth; `clean` and `surface` then work on that native-grid mask as before, and
     "logits" / "prob" are native-grid values.  A list of volumes takes one spacing for all or a list of them.  A resampler
     without a spacing and a spacing without a resampler are refused; `resample=None` launches nothing new and returns today's
-    results bit for bit."""
+    results bit for bit.
+
+    `window`: a (lo, hi) pair or an `IntensityNormalizer`.  A normalizer measures every volume of a call - as passed, on its own
+    grid, before any `resample=` (three small launches and one wait for the device) - and that window serves every gather of the
+    call; with select "mask" the truth of `score` is the mask (a plain call has none and is refused).  `s(vol, ..., window=(lo, hi))`
+    and `s.score(vol, truth, ..., window=(lo, hi))` override it for that call and launch no statistics (a list of volumes takes
+    one pair for all or a list of pairs).  With a (lo, hi) pair nothing new is launched and every result is today's."""
 
     def __init__(self, model, overlap: int = 32, batch: int = 64, window=(-1024.0, 1024.0), threshold: float = 0.5,
                  label: int = -1, ensemble: int = 1, clean=None, surface=None, resample=None):
@@ -563,9 +731,8 @@ class TiledSegmenter:
             raise VuError(f"overlap must be in 0 .. im_size // 2 = {T // 2} (got {overlap})")
         if int(batch) < 1:
             raise VuError(f"batch must be at least 1 (got {batch})")
-        lo, hi = float(np.float32(window[0])), float(np.float32(window[1]))
-        if not hi > lo:
-            raise VuError(f"the intensity window must have hi > lo (got {window[0]} .. {window[1]})")
+        self.normalizer = window if isinstance(window, IntensityNormalizer) else None
+        lo_hi = None if self.normalizer is not None else window_pair(window)
         if int(label) > 255:
             raise VuError(f"label must be negative (any non-zero truth) or 0 .. 255 (got {label})")
         if ensemble not in TiledRestorer.ENSEMBLE_OPS:
@@ -579,7 +746,7 @@ class TiledSegmenter:
         self.clean, self.surface, self.resample = clean, surface, resample
         self.zthr = logit_threshold(threshold)
         self.model, self.T, self.overlap, self.batch = model, T, int(overlap), int(batch)
-        self.window, self.threshold, self.label, self.ensemble = (lo, hi), float(threshold), int(label), int(ensemble)
+        self.window, self.threshold, self.label, self.ensemble = lo_hi, float(threshold), int(label), int(ensemble)
 
     def _device(self) -> torch.device:
         dev = next(self.model.parameters()).device
@@ -597,13 +764,16 @@ class TiledSegmenter:
             raise VuError(f"empty {what} {tuple(t.shape)}")
         return t
 
-    def __call__(self, vol, output: str = "mask", spacing=None):
+    def __call__(self, vol, output: str = "mask", spacing=None, window=None):
         if isinstance(vol, (list, tuple)):
+            ws = [None] * len(vol) if window is None else VolumeResampler._per_item(window, len(vol), VolumeResampler._is_one)
             if spacing is None:
-                return [self(v, output) for v in vol]
-            return [self(v, output, s) for v, s in zip(vol, VolumeResampler._per_item(spacing, len(vol), VolumeResampler._is_one))]
+                return [self(v, output, window=w) for v, w in zip(vol, ws)]
+            return [self(v, output, s, w) for v, s, w in zip(vol, VolumeResampler._per_item(spacing, len(vol), VolumeResampler._is_one), ws)]
         if output not in ("mask", "logits", "prob"):
             raise VuError(f"output must be 'mask', 'logits' or 'prob' (got {output!r})")
+        if window is not None:
+            window = window_pair(window)
         if self.clean is not None and output != "mask":
             raise VuError(f"a cleaner works on the mask: output={output!r} with clean= is refused")
         v = self._volume(vol, torch.int16, "volume")
@@ -612,13 +782,16 @@ class TiledSegmenter:
         dev = self._device()
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
+        win = self._window_of(v, None, window)
         with torch.no_grad():
             if output == "mask":
-                m = (self._run(v, None, mask=True) if wshape is None else self._run_resampled(v, wshape, None, mask=True))["mask"]
+                m = (self._run(v, None, mask=True, window=win) if wshape is None
+                     else self._run_resampled(v, wshape, None, mask=True, window=win))["mask"]
                 if self.clean is not None:
                     m = self.clean.run(m, None, out=m)["mask"]
                 return m.reshape(shape)
-            z = (self._run(v, None, logits=True) if wshape is None else self._run_resampled(v, wshape, None, logits=True))["logits"]
+            z = (self._run(v, None, logits=True, window=win) if wshape is None
+                 else self._run_resampled(v, wshape, None, logits=True, window=win))["logits"]
             z = z.reshape(shape)
             return z if output == "logits" else torch.sigmoid(z)
 
@@ -633,15 +806,26 @@ class TiledSegmenter:
         w = self.resample.out_shape(shape, spacing)
         return (1,) * (3 - len(w)) + w
 
-    def _run_resampled(self, vol: torch.Tensor, wshape, truth, logits: bool = False, mask: bool = False):
+    def _window_of(self, vol: torch.Tensor, truth, window):
+        """The (lo, hi) of one call: the per-call pair, else the constructor's pair, else the normalizer's measurement of the
+        (D,H,W) device volume as passed (its truth is the mask of select "mask")."""
+        if window is not None:
+            return window_pair(window)
+        if self.normalizer is None:
+            return self.window
+        return self.normalizer.window(vol, truth)
+
+    def _run_resampled(self, vol: torch.Tensor, wshape, truth, logits: bool = False, mask: bool = False, window=None):
         """`_run` at the working spacing: vu_resample_i16 to `wshape`, the logits there, one vu_resample_f32 back to vol's
         shape -> what `_run` returns, on the native grid."""
         with torch.cuda.device(vol.device):
             work = VolumeResampler.run_i16(vol, wshape)
-            z = self._run(work, None, logits=True)["logits"]
+            z = self._run(work, None, logits=True, window=window)["logits"]
             return VolumeResampler.run_f32(z, tuple(vol.shape), truth, self.zthr, self.label, logits=logits, mask=mask)
 
-    def score(self, vol, truth, spacing=None):
+    def score(self, vol, truth, spacing=None, window=None):
+        if window is not None:
+            window = window_pair(window)
         v, t = self._volume(vol, torch.int16, "volume"), self._volume(truth, torch.uint8, "truth")
         if tuple(v.shape) != tuple(t.shape):
             raise VuError(f"the truth {tuple(t.shape)} does not have the volume's shape {tuple(v.shape)}")
@@ -653,8 +837,9 @@ class TiledSegmenter:
         shape = tuple(v.shape)
         v = v.to(dev, non_blocking=True).contiguous().reshape((-1,) + shape[-2:])
         t = t.to(dev, non_blocking=True).contiguous().reshape(v.shape)
+        win = self._window_of(v, t, window)
         with torch.no_grad():
-            res = self._run(v, t, mask=True) if wshape is None else self._run_resampled(v, wshape, t, mask=True)
+            res = self._run(v, t, mask=True, window=win) if wshape is None else self._run_resampled(v, wshape, t, mask=True, window=win)
             if self.clean is not None:
                 raw = res["counts"].cpu()
                 out = MaskCleaner.finish(self.clean.run(res["mask"], t, self.label, out=res["mask"]), shape)
@@ -673,7 +858,7 @@ class TiledSegmenter:
         if c is not None and c.connectivity in (6, 26) and (v.dim() == 2 or v.shape[0] == 1):
             raise VuError(f"connectivity {c.connectivity} needs a (D,H,W) volume with D >= 2 (got {tuple(v.shape)}); a slice takes 4 or 8")
 
-    def _run(self, vol: torch.Tensor, truth, logits: bool = False, mask: bool = False):
+    def _run(self, vol: torch.Tensor, truth, logits: bool = False, mask: bool = False, window=None):
         L, T, ov, m = lib(), self.T, self.overlap, self.model
         D, H, W = (int(s) for s in vol.shape)
         ny, nx = C.c_int(0), C.c_int(0)
@@ -681,7 +866,7 @@ class TiledSegmenter:
         nt = ny.value * nx.value
         G = max(1, self.batch // nt)
         dev, st = vol.device, stream_ptr(vol.device)
-        lo, hi = self.window
+        lo, hi = window if window is not None else self._window_of(vol, truth, None)
         m._ensure_flat()
         outs = torch.empty(min(G, D) * nt, 1, T, T, dtype=torch.float32, device=dev)
         x = torch.empty(min(self.batch, outs.shape[0]), 1, T, T, dtype=torch.float32, device=dev)
